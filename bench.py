@@ -14,7 +14,14 @@ weights (the checkpoint is a download; workload/weights.py).  Frames are residen
 timed region.  N>1: independent clips, one per GPU (replicas; RCCL is used only for the barrier
 and the max-over-ranks reduction) -> "scaling": "weak".
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line; `ms_per_step` = timed milliseconds / K.
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's clip) as DIR/<name>.npy, float32:
+prob.npy = the [objects + 1, H, W] probabilities of `step()`.  Inputs and weights are seeded, so two builds run
+with the same arguments can be compared output for output.  A clip of more than 128 frames runs back and forth over
+its first 128 (make_headline_clip).  Everything below (`roofline`, `affinity`,
+`cpu_baseline`, `also`, `also_kernels`, `timed_like_eval_vos`, `also_multi_gpu`) is measured only with `--full`.
+
+Extra objects on the JSON line (--full):
   roofline      dominant kernel (conv implicit GEMM, fp32 MFMA): algorithmic FLOPs of every launch
                 / its HIP-event duration.  The events are recorded on the launch stream around every
                 deva_conv2d call WITHOUT any synchronisation, in a pass that replays the same number of
@@ -133,6 +140,18 @@ def make_clip(height, width, n_frames, seed, device):
     from workload import synth
     stream = synth.FrameStream(height, width, seed=seed)
     return [stream.next().to(device) for _ in range(n_frames)]
+
+
+HEADLINE_DISTINCT_FRAMES = 128  # the frame stream is sequential on the host (~20 ms per 480p frame)
+
+
+def make_headline_clip(height, width, n_frames, seed, device):
+    """the headline clip: the first HEADLINE_DISTINCT_FRAMES frames of make_clip, a longer clip runs back and forth over
+    them (0 .. P-1, P-2 .. 1, 0 ..: temporally coherent, no cut), so that set-up time does not grow with --steps"""
+    p = min(n_frames, HEADLINE_DISTINCT_FRAMES)
+    pool = make_clip(height, width, p, seed, device)
+    period = max(2 * (p - 1), 1)
+    return [pool[min(t % period, period - t % period)] for t in range(n_frames)]
 
 
 def start_clip(net, cfg, frames, num_objects, device, lt_prefill=0, shard=None):
@@ -617,10 +636,31 @@ def whole_job_fps(steps_per_rank: int, world: int, elapsed: float) -> float:
     return world * steps_per_rank / elapsed
 
 
-def run_long4k(net, device, steps, warmup, seed, shard, dist, size=(2160, 3840), bank_tokens=50000):
+DUMP_BYTES = 60 << 20  # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float32 (float64 stays float64).  Outputs larger
+    than DUMP_BYTES in all are cut to the same fraction of every array's flat elements, drawn with a fixed seed (the
+    same indices on every run of the same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().cpu() for k, v in arrays.items()}
+    host = {k: (v if v.dtype == torch.float64 else v.float()).numpy() for k, v in host.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BYTES:
+            keep = max(1, a.size * DUMP_BYTES // total)
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+
+
+def run_long4k(net, device, steps, warmup, seed, shard, dist, size=(2160, 3840), bank_tokens=50000, outputs=None):
     """BASELINE configs[4]: one 4K clip, 1 object, 50 000-token long-term bank.  shard = None (one GPU) |
     'owner' | 'queries' | 'bank' (MemoryManager modes, all ranks of the group step the same clip).
-    -> (FPS, bank sizes at the end, collective bytes this rank moved per timed frame)"""
+    -> (FPS, bank sizes at the end, collective bytes this rank moved per timed frame); outputs['prob'] = what the last
+    timed step returned, when a dict is given"""
     from workload import synth
     cfg = synth.base_config(max_long_term_elements=bank_tokens)
     n_frames = 1 + warmup + steps
@@ -629,12 +669,15 @@ def run_long4k(net, device, steps, warmup, seed, shard, dist, size=(2160, 3840),
     for t in range(1, 1 + warmup):
         core.step(frames[t])
     comm0 = core.memory.comm_bytes
+    last = {}
 
     def timed_steps():
         for t in range(1 + warmup, n_frames):
-            core.step(frames[t])
+            last['prob'] = core.step(frames[t])
 
     elapsed = timed_region(timed_steps, dist, device)
+    if outputs is not None:
+        outputs.update(last)
     mem = core.memory
     bank = {'long': {b: mem.long_mem.size(b) for b in mem.long_mem.buckets},
             'work': {b: mem.work_mem.size(b) for b in mem.work_mem.buckets}}
@@ -853,7 +896,10 @@ def long4k(args, net, rank, world, device, dist):
     """`--workload long4k`: strong scaling of ONE clip over the GPUs of the node"""
     mode = args.long4k_mode if dist is not None else None
     tiny = dict(size=(96, 128), bank_tokens=600) if os.environ.get('DEVA_BENCH_EMULATED') == '1' else {}  # (CPU test)
-    fps, bank, comm = run_long4k(net, device, args.steps, args.warmup, seed=11, shard=mode, dist=dist, **tiny)
+    outputs = {}
+    fps, bank, comm = run_long4k(net, device, args.steps, args.warmup, seed=11, shard=mode, dist=dist, outputs=outputs, **tiny)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     what = {None: 'one GPU', 'owner': 'frame owner (rank 0 encodes / decodes) + query-sharded read',
             'queries': 'every rank steps the clip, query-sharded read',
             'bank': 'every rank steps the clip, token-sharded read (candidate keys all-gathered, exact merge)',
@@ -1101,21 +1147,27 @@ def main():
     ap.add_argument('--no_cpu_baseline', action='store_true')
     ap.add_argument('--no_extra', action='store_true')
     ap.add_argument('--no_affinity', action='store_true', help='skip the affinity / pointwise micro-benchmarks (profiling passes)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: roofline replay, MFMA probe, eval_vos-style timing, micro-benchmarks, the `also` '
+                         'lines, the CPU baseline and (N > 1) the one-clip 4K line; --no_* switch parts of it off')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
 
     torch.set_grad_enabled(False)
     emulated = os.environ.get('DEVA_BENCH_EMULATED') == '1'  # tests/test_replicas_gloo.py only: launch path on CPU/gloo
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        # `python bench.py --gpus N` (the driver's form without torchrun): become N ranks, one per GPU
+        # `python bench.py --gpus N` (the driver's form without torchrun): launch N ranks, one per GPU, as child processes
+        # (never exec over this process: the device query below may already have initialised the GPU runtime here)
         if not emulated and torch.cuda.device_count() < args.gpus:
             sys.exit(f'bench.py --gpus {args.gpus}: only {torch.cuda.device_count()} GPU(s) visible')
         import socket
+        import subprocess
         with socket.socket() as sock:
             sock.bind(('127.0.0.1', 0))
             port = sock.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
-                                  f'--nproc-per-node={args.gpus}', '--master-addr', '127.0.0.1', '--master-port', str(port),
-                                  os.path.abspath(__file__), *sys.argv[1:]])
+        cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}',
+               '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__), *sys.argv[1:]]
+        sys.exit(subprocess.call(cmd))
     rank = int(os.environ.get('RANK', 0))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -1144,17 +1196,21 @@ def main():
         return long4k(args, net, rank, world, device, dist if distributed else None)
     cfg = synth.base_config(enable_long_term=False, enable_long_term_count_usage=False)
     n_frames = 1 + args.warmup + args.steps
-    frames = make_clip(args.height, args.width, n_frames, seed=100 + rank, device=device)  # HBM resident
+    frames = make_headline_clip(args.height, args.width, n_frames, seed=100 + rank, device=device)  # HBM resident
 
     core = start_clip(net, cfg, frames, args.objects, device)
     for t in range(1, 1 + args.warmup):
         core.step(frames[t])
 
+    last = {}
+
     def timed_steps():
         for t in range(1 + args.warmup, n_frames):
-            core.step(frames[t])
+            last['prob'] = core.step(frames[t])
 
     elapsed = timed_region(timed_steps, dist if distributed else None, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     bank = {b: core.memory.work_mem.size(b) for b in core.memory.work_mem.buckets}
 
     result = {
@@ -1179,7 +1235,7 @@ def main():
         },
         'rccl_ranks': world if distributed else 0,
     }
-    if distributed and not args.no_extra:
+    if distributed and args.full and not args.no_extra:
         # BASELINE configs[4]: ONE 4K clip on all ranks, frame-owner mode; every rank takes part
         steps4k = max(2, min(20, args.steps))
         tiny = dict(size=(96, 128), bank_tokens=600) if emulated else {}  # (the CPU test of this launch path)
@@ -1191,7 +1247,7 @@ def main():
              'config': {'workload': 'BASELINE configs[4]: frame owner (rank 0 encodes / decodes) + query-sharded read',
                         'bank_tokens_at_end': bank_own, 'collective_bytes_per_frame_rank0': comm_own}}]
 
-    if rank == 0 and emulated:
+    if rank == 0 and (emulated or not args.full):
         emit(result)
     elif rank == 0:
         # ---- roofline of the dominant kernel: event-timed replay of as many frames, continuing the same clip

@@ -57,7 +57,7 @@ print('read_total', r.get('read_total'))
 PY
 fi
 if has bench; then
-  DEVA_BENCH_LAYERS=$OUT/conv_layers_480p5.json timeout -k 10 ${BENCH_TIMEOUT:-1200} python bench.py ${BENCH_ARGS:---steps 40 --warmup 5} > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"; cp bench_extra.json $OUT/bench_extra.json 2>/dev/null
+  DEVA_BENCH_LAYERS=$OUT/conv_layers_480p5.json timeout -k 10 ${BENCH_TIMEOUT:-1200} python bench.py --full ${BENCH_ARGS:---steps 40 --warmup 5} > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"; cp bench_extra.json $OUT/bench_extra.json 2>/dev/null
   python - <<'PY'
 import json
 d = json.loads(open('gpurun_out/r06/bench.json').read().strip().split('\n')[-1])
