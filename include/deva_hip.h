@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DEVA_HIP_ABI_VERSION 9
+#define DEVA_HIP_ABI_VERSION 10
 
 int deva_hip_version(void);
 const char* deva_hip_last_error(void);
@@ -212,6 +212,13 @@ int deva_upsample2x_add(const float* in, const float* skip, float* out, int batc
  * ds2 is bit-identical to deva_area_downsample(in, ..., 2). */
 int deva_upsample2x_add_ds2(const float* in, const float* skip, float* out, float* ds2, int batch, int channels, int height,
                             int width, void* stream);
+/* Several clips in one decoder pass (deva/inference/multi_clip.py): skip is [S][C][2h][2w] and skip_index an int32 [batch]
+ * on the device (0 <= skip_index[b] < S); output item b adds skip[skip_index[b]].  Each item is bit-identical to
+ * deva_upsample2x_add(_ds2) with skip[skip_index[b]] as the broadcast skip; ds2 is bit-identical to deva_area_downsample. */
+int deva_upsample2x_add_map(const float* in, const float* skip, const int32_t* skip_index, float* out, int batch, int channels,
+                            int height, int width, void* stream);
+int deva_upsample2x_add_ds2_map(const float* in, const float* skip, const int32_t* skip_index, float* out, float* ds2, int batch,
+                                int channels, int height, int width, void* stream);
 
 /* F.interpolate(mode='area') for an integer shrink factor (network.py:117,
  * group_modules.py:33-38): mean over factor x factor boxes.  in [planes][H][W]. */

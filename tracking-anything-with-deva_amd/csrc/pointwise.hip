@@ -149,8 +149,12 @@ __device__ __forceinline__ float bilerp(const float* __restrict__ src, int W, co
   return ly.w0 * top + ly.w1 * bot;
 }
 
+// MAP (deva_upsample2x_add_map): skip holds S planes-of-C and plane b*C + c adds skip plane skip_index[b]*C + c; without
+// MAP skip is one [C][2h][2w] block broadcast over the batch (skip_index unused)
+template <bool MAP>
 __global__ void upsample2x_add_kernel(const float* __restrict__ in, const float* __restrict__ skip,
-                                      float* __restrict__ out, int64_t total, int C, int h, int w) {
+                                      const int* __restrict__ skip_index, float* __restrict__ out, int64_t total, int C,
+                                      int h, int w) {
   const int OH = 2 * h, OW = 2 * w;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int ox = (int)(i % OW);
@@ -160,7 +164,8 @@ __global__ void upsample2x_add_kernel(const float* __restrict__ in, const float*
     const int c = (int)(plane % C);
     const Lerp ly = lerp_index(oy, 0.5f, h), lx = lerp_index(ox, 0.5f, w);
     float v = bilerp(in + plane * (int64_t)h * w, w, ly, lx);
-    if (skip) v = skip[((int64_t)c * OH + oy) * OW + ox] + v;
+    const int64_t sc = MAP ? (int64_t)skip_index[plane / C] * C + c : (int64_t)c;
+    if (skip) v = skip[(sc * OH + oy) * OW + ox] + v;
     out[i] = v;
   }
 }
@@ -177,7 +182,9 @@ __global__ void upsample2x_add_kernel(const float* __restrict__ in, const float*
 // no extra loads, the same sum in the same order as area_downsample_kernel, and one pass over `in` less.
 typedef float up_f32x4 __attribute__((ext_vector_type(4)));
 typedef up_f32x4 up_f32x4_u __attribute__((aligned(4)));
+template <bool MAP>  // (see upsample2x_add_kernel)
 __global__ __launch_bounds__(256) void upsample2x_add_quad_kernel(const float* __restrict__ in, const float* __restrict__ skip,
+                                                                  const int* __restrict__ skip_index,
                                                                   float* __restrict__ out, float* __restrict__ ds2, int C,
                                                                   int h, int w) {
   const int OH = 2 * h, OW = 2 * w, QW = OW >> 2;
@@ -223,7 +230,8 @@ __global__ __launch_bounds__(256) void upsample2x_add_quad_kernel(const float* _
     const int64_t ofs = ((int64_t)plane * OH + oy) * OW + 4 * j;
     up_f32x4 r = {v[0], v[1], v[2], v[3]};
     if (skip) {
-      const up_f32x4 sk = *reinterpret_cast<const up_f32x4*>(skip + ((int64_t)(plane % C) * OH + oy) * OW + 4 * j);
+      const int64_t sc = MAP ? (int64_t)skip_index[plane / C] * C + plane % C : (int64_t)(plane % C);
+      const up_f32x4 sk = *reinterpret_cast<const up_f32x4*>(skip + (sc * OH + oy) * OW + 4 * j);
       r = up_f32x4{sk[0] + v[0], sk[1] + v[1], sk[2] + v[2], sk[3] + v[3]};
     }
     *reinterpret_cast<up_f32x4*>(out + ofs) = r;
@@ -720,19 +728,20 @@ extern "C" int deva_maxpool3x3s2(const float* in, float* out, int64_t planes, in
   return check_launch("deva_maxpool3x3s2");
 }
 
-static int upsample2x_add_impl(const float* in, const float* skip, float* out, float* ds2, int batch, int channels, int height,
-                               int width, void* stream, const char* what) {
+template <bool MAP>
+static int upsample2x_add_impl(const float* in, const float* skip, const int* skip_index, float* out, float* ds2, int batch,
+                               int channels, int height, int width, void* stream, const char* what) {
   const int64_t total = (int64_t)batch * channels * height * 2 * width * 2;
   const int64_t planes = (int64_t)batch * channels;
   const bool aligned = (((uintptr_t)out | (uintptr_t)skip) & 15) == 0;  // 16-byte rows: OW % 4 == 0 and aligned bases
   if (width % 2 == 0 && width >= 4 && planes <= 65535 && aligned && (!ds2 || height % 2 == 0)) {
     const int quads = (height + 1) * (width * 2 / 4);  // (row pair, pixel quad): output rows 2P - 1 and 2P, P = 0 .. height
-    hipLaunchKernelGGL(upsample2x_add_quad_kernel, dim3((unsigned)ceil_div(quads, 256), (unsigned)planes), dim3(256), 0,
-                       (hipStream_t)stream, in, skip, out, ds2, channels, height, width);
+    hipLaunchKernelGGL(upsample2x_add_quad_kernel<MAP>, dim3((unsigned)ceil_div(quads, 256), (unsigned)planes), dim3(256), 0,
+                       (hipStream_t)stream, in, skip, skip_index, out, ds2, channels, height, width);
     return check_launch(what);
   }
-  hipLaunchKernelGGL(upsample2x_add_kernel, grid_for(total), dim3(TPB), 0, (hipStream_t)stream, in, skip, out,
-                     total, channels, height, width);
+  hipLaunchKernelGGL(upsample2x_add_kernel<MAP>, grid_for(total), dim3(TPB), 0, (hipStream_t)stream, in, skip, skip_index,
+                     out, total, channels, height, width);
   if (check_launch(what)) return 1;
   if (ds2) return deva_area_downsample(in, ds2, planes, height, width, 2, stream);  // (shapes the quad kernel does not take)
   return 0;
@@ -741,14 +750,37 @@ static int upsample2x_add_impl(const float* in, const float* skip, float* out, f
 extern "C" int deva_upsample2x_add(const float* in, const float* skip, float* out, int batch, int channels,
                                    int height, int width, void* stream) {
   DEVA_REQUIRE(in && out && batch > 0 && channels > 0 && height > 0 && width > 0, "deva_upsample2x_add: bad args");
-  return upsample2x_add_impl(in, skip, out, nullptr, batch, channels, height, width, stream, "deva_upsample2x_add");
+  return upsample2x_add_impl<false>(in, skip, nullptr, out, nullptr, batch, channels, height, width, stream,
+                                    "deva_upsample2x_add");
 }
 
 extern "C" int deva_upsample2x_add_ds2(const float* in, const float* skip, float* out, float* ds2, int batch, int channels,
                                        int height, int width, void* stream) {
   DEVA_REQUIRE(in && out && ds2 && batch > 0 && channels > 0 && height > 0 && width > 0, "deva_upsample2x_add_ds2: bad args");
   DEVA_REQUIRE(height % 2 == 0 && width % 2 == 0, "deva_upsample2x_add_ds2: even input size expected");
-  return upsample2x_add_impl(in, skip, out, ds2, batch, channels, height, width, stream, "deva_upsample2x_add_ds2");
+  return upsample2x_add_impl<false>(in, skip, nullptr, out, ds2, batch, channels, height, width, stream,
+                                    "deva_upsample2x_add_ds2");
+}
+
+// several clips in one decoder pass (deva/inference/multi_clip.py): skip [S][C][2h][2w], output plane b*C + c adds
+// skip plane skip_index[b]*C + c (int32 on the device, 0 <= skip_index[b] < S -- the caller's contract); the same
+// kernels and per-pixel arithmetic as deva_upsample2x_add / _ds2, so every plane is bit-identical to the broadcast call
+// with skip[skip_index[b]]
+extern "C" int deva_upsample2x_add_map(const float* in, const float* skip, const int32_t* skip_index, float* out, int batch,
+                                       int channels, int height, int width, void* stream) {
+  DEVA_REQUIRE(in && skip && skip_index && out && batch > 0 && channels > 0 && height > 0 && width > 0,
+               "deva_upsample2x_add_map: bad args");
+  return upsample2x_add_impl<true>(in, skip, skip_index, out, nullptr, batch, channels, height, width, stream,
+                                   "deva_upsample2x_add_map");
+}
+
+extern "C" int deva_upsample2x_add_ds2_map(const float* in, const float* skip, const int32_t* skip_index, float* out,
+                                           float* ds2, int batch, int channels, int height, int width, void* stream) {
+  DEVA_REQUIRE(in && skip && skip_index && out && ds2 && batch > 0 && channels > 0 && height > 0 && width > 0,
+               "deva_upsample2x_add_ds2_map: bad args");
+  DEVA_REQUIRE(height % 2 == 0 && width % 2 == 0, "deva_upsample2x_add_ds2_map: even input size expected");
+  return upsample2x_add_impl<true>(in, skip, skip_index, out, ds2, batch, channels, height, width, stream,
+                                   "deva_upsample2x_add_ds2_map");
 }
 
 extern "C" int deva_area_downsample(const float* in, float* out, int64_t planes, int height, int width,

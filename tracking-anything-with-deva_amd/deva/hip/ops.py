@@ -13,7 +13,7 @@ import torch
 from . import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SQUARE_PLUS_ONE, KLAYOUT_CHUNK32, KLAYOUT_Q4, KLAYOUT_TAP_MAJOR,
                ConvDesc, DevaHipError, check, lib)
 
-__all__ = ['PackedConv', 'pack_conv', 'conv2d', 'split_fallbacks', 'PackedStem', 'pack_stem', 'stem7x7', 'pad2d', 'usage_init', 'gather_s2', 'maxpool3x3s2', 'upsample2x_add', 'upsample2x_add_ds2', 'area_downsample',
+__all__ = ['PackedConv', 'pack_conv', 'conv2d', 'split_fallbacks', 'PackedStem', 'pack_stem', 'stem7x7', 'pad2d', 'usage_init', 'gather_s2', 'maxpool3x3s2', 'upsample2x_add', 'upsample2x_add_ds2', 'clip_index', 'upsample2x_add_map', 'upsample2x_add_ds2_map', 'area_downsample',
            'aggregate', 'softmax_channels', 'upsample4x_softmax', 'cbam', 'gru_update',
            'affinity_topk', 'BankPrep', 'affinity_dense', 'affinity_candidates', 'affinity_merge', 'usage_update', 'readout_sparse', 'bank_append', 'bank_gather_rows',
            'bank_export', 'rank', 'rank_select', 'evict_select', 'similarity_dense', 'softmax_columns',
@@ -492,6 +492,45 @@ def upsample2x_add_ds2(x: torch.Tensor, skip: Optional[torch.Tensor]) -> Tuple[t
     out = _alloc((b, c, 2 * h, 2 * w), x.device)
     ds2 = _alloc((b, c, h // 2, w // 2), x.device)
     check(lib().deva_upsample2x_add_ds2(_p(x), _p(skip), _p(out), _p(ds2), b, c, h, w, _stream()), 'deva_upsample2x_add_ds2')
+    return out, ds2
+
+
+def clip_index(index, n_items: int, device) -> torch.Tensor:
+    """host list of item indices (one per batch entry, each in [0, n_items)) -> int32 device tensor for the *_map ops;
+    the range is checked here, on the host, because the kernels index with it unchecked"""
+    index = [int(i) for i in index]
+    if not index or min(index) < 0 or max(index) >= n_items:
+        raise DevaHipError(f'clip_index: indices {index} outside [0, {n_items})')
+    return torch.tensor(index, dtype=torch.int32).to(device, non_blocking=True)
+
+
+def _map_args(x: torch.Tensor, skip: torch.Tensor, skip_index: torch.Tensor, what: str):
+    b, c, h, w = x.shape
+    if skip.dim() != 4 or tuple(skip.shape[1:]) != (c, 2 * h, 2 * w) or not skip.is_contiguous():
+        raise DevaHipError(f'{what}: skip must be a contiguous [S,C,2h,2w]')
+    if skip_index.dtype != torch.int32 or tuple(skip_index.shape) != (b,) or not skip_index.is_cuda:
+        raise DevaHipError(f'{what}: skip_index must be an int32 HIP tensor [batch] (ops.clip_index)')
+    return b, c, h, w
+
+
+def upsample2x_add_map(x: torch.Tensor, skip: torch.Tensor, skip_index: torch.Tensor) -> torch.Tensor:
+    """x [B,C,h,w] -> [B,C,2h,2w] bilinear + skip[skip_index[b]] (skip [S,C,2h,2w]; skip_index from `clip_index`)"""
+    b, c, h, w = _map_args(x, skip, skip_index, 'upsample2x_add_map')
+    out = _alloc((b, c, 2 * h, 2 * w), x.device)
+    check(lib().deva_upsample2x_add_map(_p(x), _p(skip), _p(skip_index, torch.int32), _p(out), b, c, h, w, _stream()),
+          'deva_upsample2x_add_map')
+    return out
+
+
+def upsample2x_add_ds2_map(x: torch.Tensor, skip: torch.Tensor, skip_index: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(upsample2x_add_map(x, skip, skip_index), area_downsample(x, 2)) from one pass over x; h, w even"""
+    b, c, h, w = _map_args(x, skip, skip_index, 'upsample2x_add_ds2_map')
+    if h % 2 or w % 2:
+        raise DevaHipError('upsample2x_add_ds2_map: even input size expected')
+    out = _alloc((b, c, 2 * h, 2 * w), x.device)
+    ds2 = _alloc((b, c, h // 2, w // 2), x.device)
+    check(lib().deva_upsample2x_add_ds2_map(_p(x), _p(skip), _p(skip_index, torch.int32), _p(out), _p(ds2), b, c, h, w,
+                                            _stream()), 'deva_upsample2x_add_ds2_map')
     return out, ds2
 
 

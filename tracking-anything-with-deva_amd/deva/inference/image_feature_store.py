@@ -72,6 +72,15 @@ class ImageFeatureStore:
         e = self._entry(index, image)
         return e.key, e.shrinkage, e.selection
 
+    def __contains__(self, index) -> bool:
+        """the frame's features are stored or being computed (prefetch): a `get_*` of it runs no encoder"""
+        return index in self._store or index in self._pending
+
+    def put(self, index: int, ms_features: Iterable[torch.Tensor], pix_feat: torch.Tensor, key: torch.Tensor,
+            shrinkage: torch.Tensor, selection: torch.Tensor) -> None:
+        """store features computed elsewhere (deva/inference/multi_clip.py: one key-encoder pass over several clips)"""
+        self._store[index] = _FrameFeatures(tuple(ms_features), pix_feat, key, shrinkage, selection)
+
     def delete(self, index) -> None:
         self._pending.pop(index, None)
         self._store.pop(index, None)

@@ -371,3 +371,79 @@ class CompiledGraph:
         if update_sensory:
             sensory = self.sensory_update(p16, p8, p4, logits, sensory, p8_ds)
         return sensory, logits
+
+    # ---------------------------------------------------------------- several clips in one pass (deva/inference/multi_clip.py)
+    # x below is [B,C,h,w]: one image feature per clip (a batch-strided view of the batched key encoder's output is fine, the
+    # convolutions take a batch stride); `clip` is the host list of each object's clip (index into x), and `clip_dev` the
+    # same as an int32 device tensor (ops.clip_index) for the mapped up-sampling kernels.
+    @staticmethod
+    def _per_object(t, clip):
+        """t [B,...] per clip -> what object i reads as t[clip[i]]: t itself when it broadcasts (B = 1), a slice when the
+        objects are consecutive clips, otherwise a row gather"""
+        if t.shape[0] == 1:
+            return t
+        lo = clip[0]
+        if clip == list(range(lo, lo + len(clip))):
+            return t[lo:lo + len(clip)]
+        out = ops._alloc((len(clip), *t.shape[1:]), t.device)
+        ops.bank_gather_rows(t.reshape(t.shape[0], -1), ops.clip_index(clip, t.shape[0], t.device),
+                             out.view(len(clip), -1), len(clip))
+        return out
+
+    def _conv_shared_x_multi(self, base: str, x, g, clip, **kw):
+        """conv over the virtual cat(x[clip[i]], g[i]): the image part once per clip (batch B), entering object i's
+        convolution as its fused residual (the split of `_conv_shared_x`, whatever the number of objects)"""
+        amp, sp = self._amp_of(base), self._split_of(base)
+        wx, wg = self.split[base]
+        act = kw.pop('act', 0)
+        shared = ops.conv2d(wx, x, amp=amp, split=sp, **kw)
+        return ops.conv2d(wg, g, residual=self._per_object(shared, clip), amp=amp, split=sp, act=act, **kw)
+
+    def _fusion_multi(self, pre: str, x, g, clip):
+        b1 = pre + '.block1'
+        t = self._conv_shared_x_multi(b1 + '.conv1', x, g, clip, pad=1, relu_in=True, act=ACT_RELU)
+        skip = self._conv_shared_x_multi(b1 + '.downsample', x, g, clip)
+        g = self._conv(b1 + '.conv2', t, pad=1, residual=skip)
+        a = pre + '.attention.ChannelGate.mlp.'
+        g = ops.cbam(g, self.vecs[a + '1.weight'], self.vecs[a + '1.bias'], self.vecs[a + '3.weight'],
+                     self.vecs[a + '3.bias'], self.convs[pre + '.attention.SpatialGate.spatial.conv'])
+        return self._res_block(pre + '.block2', g)
+
+    def decoder_skips(self, f8, f4):
+        """the image-only inputs of the decoder's up-sampling blocks, once per clip: f8 / f4 [B,...] -> d8, d4"""
+        md = 'mask_decoder.decoder_feat_proc.transforms.'
+        return self._conv(md + '0', f8), self._conv(md + '1', f4)
+
+    def decode_multi(self, f16, d8, d4, clip, clip_dev, readout, sensory, last_mask16, update_sensory: bool):
+        """`decode` over the objects of several clips: f16 / d8 / d4 [B,...] per clip, readout / sensory / last_mask16 per
+        object (object i belongs to clip[i]) -> sensory' (or the input sensory), object logits [no,1,4h,4w]"""
+        md = 'mask_decoder'
+        p16 = self._conv(md + '.sensory_compress', sensory, last_mask16, residual=readout)
+        p16 = self._fusion_multi(md + '.fuser', f16, p16, clip)
+        p8 = self._res_block(md + '.up_16_8.out_conv', ops.upsample2x_add_map(p16, d8, clip_dev))
+        if update_sensory and p8.shape[-2] % 2 == 0 and p8.shape[-1] % 2 == 0:
+            up, p8_ds = ops.upsample2x_add_ds2_map(p8, d4, clip_dev)
+        else:
+            up, p8_ds = ops.upsample2x_add_map(p8, d4, clip_dev), None
+        p4 = self._res_block(md + '.up_8_4.out_conv', up)
+        logits = self._conv(md + '.pred', p4, pad=1, relu_in=True)
+        if update_sensory:
+            sensory = self.sensory_update(p16, p8, p4, logits, sensory, p8_ds)
+        return sensory, logits
+
+    def encode_mask_multi(self, images, f16, clip, sensory, masks, deep_update: bool):
+        """`encode_mask` over the objects of several clips: images [B,3,H,W] and f16 [B,...] per clip; sensory / masks per
+        object (object i belongs to clip[i]) -> value [no,C,h,w], sensory'"""
+        me = 'mask_encoder'
+        if (me + '.conv1') in self.stems:
+            g = ops.stem7x7(self.stems[me + '.conv1'], self._per_object(images, clip), masks)
+        else:
+            g = self._conv_shared_x_multi(me + '.conv1', images, masks, clip, stride=2, pad=3)
+        g = ops.maxpool3x3s2(g, relu_after=True)
+        g = self._stage(me + '.layer1', g, 2, 1, self._basic)
+        g = self._stage(me + '.layer2', g, 2, 2, self._basic)
+        g = self._stage(me + '.layer3', g, 2, 2, self._basic)
+        value = self._fusion_multi(me + '.fuser', f16, g, clip)
+        if deep_update:
+            sensory = self._gru(me + '.sensory_update.transform', value, sensory)
+        return value, sensory
