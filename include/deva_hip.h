@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DEVA_HIP_ABI_VERSION 10
+#define DEVA_HIP_ABI_VERSION 11
 
 int deva_hip_version(void);
 const char* deva_hip_last_error(void);
@@ -382,6 +382,22 @@ int deva_affinity_read_stats(const uint64_t* scratch, int n_total, int hw, int k
 
 /* Usage counters of freshly appended tokens (kv_memory_store.py:93-95): use[i] = 0, life[i] = 1e-7 for i < count. */
 int deva_usage_init(float* use, float* life, int count, void* stream);
+
+/* The read without top-k (top_k = None: the full softmax over the whole bank, memory_utils.py:48-76), fused with its
+ * read-out (csrc/dense_read.hip).  Scores are the natural-order fp32 values of deva_affinity_read (fp32 MFMA chains,
+ * bsq in ATen's order); per query p[n] = exp(s[n] - max) / sum exp(s - max) over all n_long + n_work tokens of the
+ * bank [long | work] (pass 1: max and sum; pass 2: p); usage_fix[n] += p[n][q] * 2^40 summed over the queries (NULL:
+ * no usage); out[o] ([cv][hw]) = sum_n value_o(n) * p[n] for each of the n_obj objects, whose token-major value
+ * arenas ([>= n][cv], 16-B aligned, cv % 4 == 0) are val_long[o] / val_work[o] -- host arrays of device pointers.
+ * The N x HW matrix is never held whole: p goes through a scratch buffer one query chunk at a time.  scratch:
+ * deva_dense_read_scratch(n_long + n_work, hw) bytes (at most ~256 MiB whatever the shape; banks of up to ~458 000
+ * tokens).  Results do not depend on where the bank splits into long / work, bit for bit.
+ * probs (test hook, NULL otherwise): p is written there instead, [ceil(n/32)*32][ceil(hw/128)*128] floats. */
+int deva_dense_read(const float* key_long, const float* shr_long, int n_long, const float* key_work,
+                    const float* shr_work, int n_work, const float* qk, const float* qe, int hw, int n_obj,
+                    const float* const* val_long, const float* const* val_work, int cv, float* const* out,
+                    uint64_t* usage_fix, void* scratch, int64_t scratch_bytes, float* probs, void* stream);
+int64_t deva_dense_read_scratch(int n_total, int hw);
 
 /* KeyValueMemoryStore.update_bucket_usage (kv_memory_store.py:118-125) for one segment:
  * use[i] += usage_fix[offset+i] * 2^-40 (if use != NULL), life[i] += 1 (if life != NULL), and

@@ -5,6 +5,7 @@ HIP stream only; every arithmetic operation below runs in a hand-written gfx950 
 wrappers raise `DevaHipError` on non-HIP / non-contiguous / wrong-dtype tensors: there is no
 fallback path.
 """
+from ctypes import c_void_p
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -15,7 +16,7 @@ from . import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SQUARE_PLUS_ONE, KLAYOUT_CHU
 
 __all__ = ['PackedConv', 'pack_conv', 'conv2d', 'split_fallbacks', 'PackedStem', 'pack_stem', 'stem7x7', 'pad2d', 'usage_init', 'gather_s2', 'maxpool3x3s2', 'upsample2x_add', 'upsample2x_add_ds2', 'clip_index', 'upsample2x_add_map', 'upsample2x_add_ds2_map', 'area_downsample',
            'aggregate', 'softmax_channels', 'upsample4x_softmax', 'cbam', 'gru_update',
-           'affinity_topk', 'BankPrep', 'affinity_dense', 'affinity_candidates', 'affinity_merge', 'usage_update', 'readout_sparse', 'bank_append', 'bank_gather_rows',
+           'affinity_topk', 'BankPrep', 'affinity_dense', 'dense_read', 'affinity_candidates', 'affinity_merge', 'usage_update', 'readout_sparse', 'bank_append', 'bank_gather_rows',
            'bank_export', 'rank', 'rank_select', 'evict_select', 'similarity_dense', 'softmax_columns',
            'label_histogram', 'merge_paint', 'lut_remap', 'index_mask', 'input_head',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_SQUARE_PLUS_ONE']
@@ -715,6 +716,47 @@ def affinity_dense(key_long, shr_long, n_long: int, key_work, shr_work, n_work: 
                                     _p(qk), _p(qe), hw, k, _p(idx, torch.int32), _p(weight), _p(usage_fix, torch.int64),
                                     _stream()), 'deva_affinity_dense')
     return idx, weight
+
+
+_DENSE_WS = {}
+
+
+def dense_read(key_long, shr_long, n_long: int, key_work, shr_work, n_work: int, qk: torch.Tensor, qe: torch.Tensor,
+               val_long, val_work, out: torch.Tensor, usage_fix: Optional[torch.Tensor] = None,
+               return_probs: bool = False) -> Optional[torch.Tensor]:
+    """The read with top_k = None (deva_dense_read): full softmax over all n_long + n_work tokens of the bank with max
+    subtraction, fused with the read-out.  Bank arguments as `affinity_topk`; val_long / val_work: one token-major
+    [>= n, cv] value arena per object (val_long entries may be None when n_long == 0); out [objects, cv, hw(...)] is
+    written; usage_fix as `affinity_topk`.  return_probs (tests): also return the [n, hw] softmax matrix."""
+    hw = qk.shape[1]
+    if qk.shape[0] != 64 or tuple(qe.shape) != tuple(qk.shape):
+        raise DevaHipError('dense_read: queries must be [64, hw]')
+    nobj = len(val_work)
+    if len(val_long) != nobj or out.shape[0] != nobj or (nobj and out[0].numel() != out.shape[1] * hw):
+        raise DevaHipError('dense_read: need one value arena pair and one [cv, hw] output per object')
+    cv = out.shape[1] if nobj else 0
+    L = lib()
+    n = n_long + n_work
+    need = int(L.deva_dense_read_scratch(n, hw))
+    key = (qk.device, _stream(qk.device))
+    ws = _DENSE_WS.get(key)
+    if ws is None or ws.numel() * 8 < need:
+        # bounded by the library (~256 MiB at most); grown exactly, dropped first if the allocator runs short
+        _DENSE_WS.pop(key, None)
+        ws = _DENSE_WS[key] = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=qk.device)
+    probs = None
+    if return_probs:
+        probs = torch.empty(((n + 31) // 32 * 32, (hw + 127) // 128 * 128), dtype=torch.float32, device=qk.device)
+    ptrs = lambda ts: (c_void_p * max(nobj, 1))(*[_p(t) for t in ts]) if nobj else None  # noqa: E731
+    outs = [out[i] for i in range(nobj)]
+    for t in outs:
+        _p(t, name='dense_read output')
+    check(L.deva_dense_read(_p(key_long) if n_long else None, _p(shr_long) if n_long else None, n_long,
+                            _p(key_work) if n_work else None, _p(shr_work) if n_work else None, n_work,
+                            _p(qk), _p(qe), hw, nobj, ptrs(val_long if n_long else [None] * nobj),
+                            ptrs(val_work if n_work else [None] * nobj), cv, ptrs(outs), _p(usage_fix, torch.int64),
+                            _p(ws, torch.int64), ws.numel() * 8, _p(probs), _stream()), 'deva_dense_read')
+    return probs[:n, :hw] if return_probs else None
 
 
 def affinity_last_read_flag(device) -> int:

@@ -44,13 +44,21 @@ def spatial_alignment(src_ti: int, src_image: torch.Tensor, src_mask: torch.Tens
     key_rows = torch.empty((hw, ck), dtype=torch.float32, device=src_key.device)
     ops.bank_append(src_key[0].reshape(ck, hw), key_rows, 0)
     shr = src_shrinkage[0].reshape(hw).contiguous()
-    idx, weight = ops.affinity_topk(None, None, 0, key_rows, shr, hw, tar_key[0].reshape(ck, hw),
-                                    tar_selection[0].reshape(ck, hw), config['top_k'])
     readout = torch.empty((1, num_objects, cv, h16, w16), dtype=torch.float32, device=src_key.device)
-    val_rows = torch.empty((hw, cv), dtype=torch.float32, device=src_key.device)
-    for o in range(num_objects):
-        ops.bank_append(value[0, o].reshape(cv, hw), val_rows, 0)
-        ops.readout_sparse(idx, weight, None, 0, val_rows, readout[0, o].view(cv, hw))
+    if config['top_k'] is None:
+        # the reference's do_softmax without top-k (memory_utils.py:48-76): full softmax, fused with the read-out
+        val_rows = torch.empty((num_objects, hw, cv), dtype=torch.float32, device=src_key.device)
+        for o in range(num_objects):
+            ops.bank_append(value[0, o].reshape(cv, hw), val_rows[o], 0)
+        ops.dense_read(None, None, 0, key_rows, shr, hw, tar_key[0].reshape(ck, hw), tar_selection[0].reshape(ck, hw),
+                       [None] * num_objects, list(val_rows.unbind(0)), readout[0].view(num_objects, cv, hw))
+    else:
+        idx, weight = ops.affinity_topk(None, None, 0, key_rows, shr, hw, tar_key[0].reshape(ck, hw),
+                                        tar_selection[0].reshape(ck, hw), config['top_k'])
+        val_rows = torch.empty((hw, cv), dtype=torch.float32, device=src_key.device)
+        for o in range(num_objects):
+            ops.bank_append(value[0, o].reshape(cv, hw), val_rows, 0)
+            ops.readout_sparse(idx, weight, None, 0, val_rows, readout[0, o].view(cv, hw))
 
     _, _, tar_mask = network.segment(tar_ms_features, readout, sensory, src_mask,
                                      chunk_size=config['chunk_size'], update_sensory=False)

@@ -46,11 +46,19 @@ class MemoryManager:
     MAX_TOP_K_SHARDED_BANK = 32  # the hand-over format of a token-sharded bank holds <= 32 entries per range
 
     @classmethod
-    def _checked_top_k(cls, top_k) -> int:
-        if top_k is None or not 1 <= int(top_k) <= cls.MAX_TOP_K:
+    def _checked_top_k(cls, top_k) -> Optional[int]:
+        if top_k is None:  # the full softmax over the whole bank (memory_utils.py:66-72): ops.dense_read
+            return None
+        if not 1 <= int(top_k) <= cls.MAX_TOP_K:
             raise ValueError(f'top_k={top_k} is not supported by the HIP memory read: the limit is {cls.MAX_TOP_K} (1..32 on '
-                             f'the list kernels, 33..{cls.MAX_TOP_K} on the dense kernel; the reference default is 30)')
+                             f'the list kernels, 33..{cls.MAX_TOP_K} on the dense kernel, None for the full softmax; the '
+                             'reference default is 30)')
         return int(top_k)
+
+    def _refuse_sharded_full_softmax(self, top_k, mode: str) -> None:
+        if top_k is None:
+            raise ValueError(f'{mode}: top_k=None (the full-softmax read) has no sharded form; use an integer top_k or an '
+                             'unsharded MemoryManager')
 
     def __init__(self, config: Dict):
         self.sensory_dim = config['value_dim']
@@ -94,6 +102,8 @@ class MemoryManager:
         self.config_stale = True
         self.sensory_dim = config['value_dim']
         top_k = self._checked_top_k(config['top_k'])
+        if getattr(self, '_shard_group', None) is not None:
+            self._refuse_sharded_full_softmax(top_k, f'update_config (shard_{self._shard_mode})')
         if getattr(self, '_shard_mode', None) == 'bank' and self._shard_group is not None and top_k > self.MAX_TOP_K_SHARDED_BANK:
             raise ValueError(f'top_k={top_k} > {self.MAX_TOP_K_SHARDED_BANK} (the largest top_k of a token-sharded bank: its '
                              f'hand-over format holds {self.MAX_TOP_K_SHARDED_BANK} entries per range; --top_k up to '
@@ -127,6 +137,7 @@ class MemoryManager:
                     rows to the other ranks' banks.  Only `step` is routed in this mode
                     (`incorporate_detection` raises NotImplementedError)."""
         import torch.distributed as dist
+        self._refuse_sharded_full_softmax(self.top_k, 'shard_queries')
         if not dist.is_initialized():
             raise RuntimeError('shard_queries: torch.distributed is not initialised')
         if getattr(self, '_values_sharded', False):
@@ -159,6 +170,7 @@ class MemoryManager:
         half the bytes of the all-reduce every-rank-decodes needs) and nobody else receives them.  The configuration
         for a bank that outgrows one GPU: every rank stores and scores 1/world of it, one rank decodes."""
         import torch.distributed as dist
+        self._refuse_sharded_full_softmax(self.top_k, 'shard_bank')
         if self.top_k > self.MAX_TOP_K_SHARDED_BANK:
             raise ValueError(f'shard_bank: top_k={self.top_k} > {self.MAX_TOP_K_SHARDED_BANK} is served by the dense read kernel, '
                              'which has no per-shard hand-over; use shard_queries or a smaller top_k')
@@ -257,6 +269,17 @@ class MemoryManager:
     def _read_bucket(self, bucket_id: int, bucket: List[int], qk, qe, rows: torch.Tensor) -> None:
         with_long, n_long, n_work = self._bucket_extent(bucket_id)
         usage_fix = self._usage_scratch(n_long + n_work, qk.device) if self.use_long_term else None
+        if self.top_k is None:
+            # full softmax over the bank and the read-out of every object of the bucket in one call
+            ops.dense_read(
+                self.long_mem.key_arena(bucket_id) if with_long else None,
+                self.long_mem.shrinkage_arena(bucket_id) if with_long else None, n_long,
+                self.work_mem.key_arena(bucket_id), self.work_mem.shrinkage_arena(bucket_id), n_work, qk, qe,
+                [self.long_mem.value_arena(obj) if with_long and obj in self.long_mem else None for obj in bucket],
+                [self.work_mem.value_arena(obj) for obj in bucket], rows.view(len(bucket), self.CV, -1), usage_fix)
+            if self.use_long_term:
+                self._apply_usage(bucket_id, usage_fix, with_long, n_long)
+            return
         idx, weight = ops.affinity_topk(
             self.long_mem.key_arena(bucket_id) if with_long else None,
             self.long_mem.shrinkage_arena(bucket_id) if with_long else None, n_long,
