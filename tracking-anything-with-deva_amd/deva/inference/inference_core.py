@@ -7,6 +7,7 @@ object_manager, image_feature_store, last_mask, frame_buffer, pad`) and the meth
 `incorporate_detection`, `add_to_temporary_buffer`, `vote_in_temporary_buffer`, `clear_buffer`,
 `enabled_long_id`, `_segment`, `_add_memory`.
 """
+import struct
 import warnings
 from typing import Dict, Iterable, List, Literal, Optional, Tuple
 
@@ -16,7 +17,7 @@ from deva.hip import ops
 from deva.inference.image_feature_store import ImageFeatureStore
 from deva.inference.memory_manager import MemoryManager
 from deva.inference.object_info import ObjectInfo
-from deva.inference.object_manager import ObjectManager
+from deva.inference.object_manager import ObjectManager, pack_objects, unpack_objects
 from deva.model.network import DEVA
 from deva.utils.tensor_utils import pad_divide_by, unpad
 
@@ -92,12 +93,28 @@ class DEVAInferenceCore:
     def vote_in_temporary_buffer(
             self, keyframe_selection: Literal['last', 'middle', 'score', 'first'] = 'first'
     ) -> Tuple[int, torch.Tensor, List[ObjectInfo]]:
+        """consensus of the buffered window -> (keyframe time index, H*W index mask, merged segments).  Frame-owner
+        mode: the owner votes (its feature store holds the window's features; the spatial alignments read one-frame
+        memories, not the sharded bank) and broadcasts the keyframe index and the segment list; the other ranks return
+        (keyframe index, None, segments)."""
         # consensus voting (deva/inference/consensus_automatic.py:82) is a caller of this path, not
         # part of it; it is resolved from whichever `deva` tree provides it.
         from deva.inference.consensus_automatic import find_consensus_auto_association
-        return find_consensus_auto_association(self.frame_buffer, network=self.network,
-                                               store=self.image_feature_store, config=self.config,
-                                               keyframe_selection=keyframe_selection)
+        if not self._frame_owner_mode():
+            return find_consensus_auto_association(self.frame_buffer, network=self.network,
+                                                   store=self.image_feature_store, config=self.config,
+                                                   keyframe_selection=keyframe_selection)
+        mem = self.memory
+        payload = None
+        if mem.is_frame_owner:
+            key_ti, mask, segments = find_consensus_auto_association(
+                self.frame_buffer, network=self.network, store=self.image_feature_store, config=self.config,
+                keyframe_selection=keyframe_selection)
+            payload = struct.pack('<q', int(key_ti)) + pack_objects(segments)
+        data = mem.broadcast_bytes(payload, self.frame_buffer[0].image.device)
+        if mem.is_frame_owner:
+            return key_ti, mask, segments
+        return struct.unpack_from('<q', data, 0)[0], None, unpack_objects(data, 8)[0]
 
     def clear_buffer(self) -> None:
         for f in self.frame_buffer:
@@ -121,12 +138,12 @@ class DEVAInferenceCore:
                               forward_mask: torch.Tensor = None, incremental: bool = False) -> torch.Tensor:
         """merge an image-level detection into the propagated state (inference_core.py:137-198):
         propagate (unless the caller did), match detected segments with tracked objects by IoU, retire
-        objects that went unseen for too long, and commit the merged masks as a memory frame"""
+        objects that went unseen for too long, and commit the merged masks as a memory frame.
+        Frame-owner mode: see `_incorporate_detection_frame_owner`."""
         from deva.inference.segment_merging import match_and_merge
-        if self.memory._shard_group is not None and self.memory._shard_owner is not None:
-            # frame-owner mode routes `step` only: non-owner ranks hold no encoder / decoder state to merge into
-            raise NotImplementedError('incorporate_detection is not available in frame-owner mode '
-                                      '(MemoryManager.shard_queries(owner=r)); use shard_queries() or shard_bank()')
+        if self._frame_owner_mode():
+            return self._incorporate_detection_frame_owner(image, new_mask, segments_info, image_ti_override,
+                                                           forward_mask, incremental)
         frame_ti, batch, ms_features, key, shrinkage, selection = self._begin_frame(image, image_ti_override)
         new_mask, _ = pad_divide_by(new_mask, 16)
 
@@ -183,17 +200,9 @@ class DEVAInferenceCore:
         mem, om = self.memory, self.object_manager
         own = mem.is_frame_owner
         annotated = mask is not None
-        self.curr_ti += 1
-        frame_ti = image_ti_override if image_ti_override is not None else self.curr_ti
-        padded, self.pad = pad_divide_by(image, 16)
-        h, w = padded.shape[-2] // 16, padded.shape[-1] // 16
         device = image.device
-        ms_features = key = shrinkage = selection = None
-        if own:
-            batch = padded.unsqueeze(0)
-            store = self.image_feature_store
-            ms_features = store.get_ms_features(frame_ti, batch)
-            key, shrinkage, selection = store.get_key(frame_ti, batch)
+        frame_ti, h, w, batch, ms_features, key, shrinkage, selection = self._begin_frame_owner(image,
+                                                                                                image_ti_override)
         due = self.curr_ti - self.last_mem_ti >= self.mem_every
         commit = (annotated or due) and not end
         propagate = (not annotated) or (om.num_obj > 0 and not om.has_all(objects))
@@ -205,16 +214,7 @@ class DEVAInferenceCore:
                 if own:
                     prob = torch.zeros((1, h * 16, w * 16), device=device, dtype=torch.float32)
             else:
-                qk, qe = mem.broadcast_query(key, selection, h, w, device)
-                readout = mem.match_memory(qk, qe)
-                if own:
-                    ids = om.all_obj_ids
-                    sensory, _, dec = self.network.segment(ms_features, om.realize_dict(readout).unsqueeze(0),
-                                                           mem.get_sensory(ids), self.last_mask,
-                                                           chunk_size=self.chunk_size, update_sensory=not end)
-                    if not end:
-                        mem.update_sensory(sensory, ids)
-                    prob = dec[0]
+                prob = self._segment_frame_owner(key, selection, ms_features, h, w, device, update_sensory=not end)
         if annotated:
             new_tmp_ids, _ = om.add_new_objects(objects)
             if own:
@@ -227,24 +227,127 @@ class DEVAInferenceCore:
         if own:
             self.last_mask = prob[1:].unsqueeze(0)
         if commit:
-            ids = om.all_obj_ids
-            if not ids:
-                warnings.warn('Empty object mask!', RuntimeWarning)
-            else:
-                value = sensory = None
-                if own:
-                    mem.initialize_sensory_if_needed(key, ids)
-                    value, sensory = self.network.encode_mask(batch, ms_features, mem.get_sensory(ids), self.last_mask,
-                                                              is_deep_update=True, chunk_size=self.chunk_size)
-                key_b, shr_b, val_b, sel_b = mem.broadcast_memory_frame(key, shrinkage, value, selection, ids, h, w,
-                                                                        device)
-                mem.add_memory(key_b, shr_b, val_b, ids, selection=sel_b)
-                self.last_mem_ti = self.curr_ti
-                if own:
-                    mem.update_sensory(sensory, ids)
+            self._add_memory_frame_owner(batch, ms_features, key, shrinkage, selection, h, w, device)
         if own and delete_buffer:
             self.image_feature_store.delete(frame_ti)
         return unpad(prob, self.pad) if own else None
+
+    # ------------------------------------------------------------------ frame-owner mode: the shared halves of a frame
+    def _frame_owner_mode(self) -> bool:
+        return self.memory._shard_group is not None and self.memory._shard_owner is not None
+
+    def _begin_frame_owner(self, image: torch.Tensor, image_ti_override):
+        """`_begin_frame` in frame-owner mode: every rank advances the clock and pads; only the owner fetches (or
+        computes) the features -> (frame_ti, h/16, w/16, batch, ms_features, key, shrinkage, selection), the last five
+        None on the other ranks"""
+        self.curr_ti += 1
+        frame_ti = image_ti_override if image_ti_override is not None else self.curr_ti
+        padded, self.pad = pad_divide_by(image, 16)
+        h, w = padded.shape[-2] // 16, padded.shape[-1] // 16
+        batch = ms_features = key = shrinkage = selection = None
+        if self.memory.is_frame_owner:
+            batch = padded.unsqueeze(0)
+            store = self.image_feature_store
+            ms_features = store.get_ms_features(frame_ti, batch)
+            key, shrinkage, selection = store.get_key(frame_ti, batch)
+        return frame_ti, h, w, batch, ms_features, key, shrinkage, selection
+
+    def _segment_frame_owner(self, key, selection, ms_features, h: int, w: int, device, update_sensory: bool = True):
+        """`_segment` on an engaged memory in frame-owner mode: the owner broadcasts the query, every rank reads its
+        share, the owner decodes -> (num_objects+1)*H*W probabilities on the owner, None elsewhere"""
+        mem, om = self.memory, self.object_manager
+        qk, qe = mem.broadcast_query(key, selection, h, w, device)
+        readout = mem.match_memory(qk, qe)
+        if not mem.is_frame_owner:
+            return None
+        ids = om.all_obj_ids
+        sensory, _, prob = self.network.segment(ms_features, om.realize_dict(readout).unsqueeze(0), mem.get_sensory(ids),
+                                                self.last_mask, chunk_size=self.chunk_size, update_sensory=update_sensory)
+        if update_sensory:
+            mem.update_sensory(sensory, ids)
+        return prob[0]
+
+    def _add_memory_frame_owner(self, batch, ms_features, key, shrinkage, selection, h: int, w: int, device) -> None:
+        """`_add_memory` of `self.last_mask` in frame-owner mode: the owner encodes the value, every rank appends the
+        broadcast rows (consolidation / eviction then run on identical inputs), the sensory state stays on the owner"""
+        mem = self.memory
+        ids = self.object_manager.all_obj_ids
+        if not ids:
+            warnings.warn('Empty object mask!', RuntimeWarning)
+            return
+        value = sensory = None
+        if mem.is_frame_owner:
+            mem.initialize_sensory_if_needed(key, ids)
+            value, sensory = self.network.encode_mask(batch, ms_features, mem.get_sensory(ids), self.last_mask,
+                                                      is_deep_update=True, chunk_size=self.chunk_size)
+        key_b, shr_b, val_b, sel_b = mem.broadcast_memory_frame(key, shrinkage, value, selection, ids, h, w, device)
+        mem.add_memory(key_b, shr_b, val_b, ids, selection=sel_b)
+        self.last_mem_ti = self.curr_ti
+        if mem.is_frame_owner:
+            mem.update_sensory(sensory, ids)
+
+    def _broadcast_decisions(self, kept: Optional[List[int]], device) -> Optional[List[int]]:
+        """frame-owner mode, detection frame: the owner's object table after merging and purging, plus the kept list
+        of the purge (None: nothing was purged), travel as bytes -- int32 length of the kept list (-1 for None), the
+        kept ids (int64), then `ObjectManager.encode_state`; the other ranks adopt the table.  -> the kept list"""
+        mem, om = self.memory, self.object_manager
+        payload = None
+        if mem.is_frame_owner:
+            ids = [] if kept is None else [int(i) for i in kept]
+            payload = struct.pack(f'<i{len(ids)}q', -1 if kept is None else len(ids), *ids) + om.encode_state()
+        data = mem.broadcast_bytes(payload, device)
+        if mem.is_frame_owner:
+            return kept
+        n = struct.unpack_from('<i', data, 0)[0]
+        kept = None if n < 0 else list(struct.unpack_from(f'<{n}q', data, 4))
+        om.load_state(data, 4 + 8 * max(n, 0))
+        return kept
+
+    def _incorporate_detection_frame_owner(self, image, new_mask, segments_info, image_ti_override, forward_mask,
+                                           incremental):
+        """`incorporate_detection` of ONE clip on several GPUs in frame-owner mode (`MemoryManager.shard_queries(group,
+        owner=r)` / `shard_bank(group, owner=r)`), on the contract of `_step_frame_owner`: every rank makes the same
+        call with the same host-side arguments (`forward_mask` None on all ranks or on none); only the owner reads
+        `new_mask`, `segments_info` and `forward_mask` -- the other ranks may pass anything there, `new_mask=None`
+        included.  Without a forward mask every rank takes part in the read of an engaged memory and the owner decodes
+        it; the owner alone merges (`match_and_merge`: ids may be drawn from np.random), applies `max_num_objects` /
+        `incremental` and purges, then broadcasts the object table and the kept list; every rank purges its memory
+        (value-sharded storage: its share of the rows) and appends the merged masks as a memory frame.  Returns the
+        probabilities on the owner, None elsewhere."""
+        from deva.inference.segment_merging import match_and_merge
+        mem, om = self.memory, self.object_manager
+        own = mem.is_frame_owner
+        device = image.device
+        frame_ti, h, w, batch, ms_features, key, shrinkage, selection = self._begin_frame_owner(image,
+                                                                                                image_ti_override)
+        if own:
+            new_mask, _ = pad_divide_by(new_mask, 16)
+        if forward_mask is None:
+            if mem.engaged:  # identical on every rank: memory frames and purges are applied everywhere
+                prob = self._segment_frame_owner(key, selection, ms_features, h, w, device)
+                if own:
+                    forward_mask = ops.index_mask(prob.contiguous())
+            elif own:
+                forward_mask = torch.zeros_like(new_mask)
+
+        kept = None
+        if own:
+            merged = match_and_merge(forward_mask, new_mask, om, segments_info,
+                                     max_num_objects=self.max_num_objects, incremental_mode=incremental)
+            anything_purged, tmp_kept, obj_kept = om.purge_inactive_objects(self.max_missed_detection_count)
+            if anything_purged:
+                kept = obj_kept
+                merged = merged[[t - 1 for t in tmp_kept]]  # tmp ids are 1-based channel numbers
+            self.last_mask = merged.unsqueeze(0).type_as(key)
+        kept = self._broadcast_decisions(kept, device)
+        if kept is not None:
+            mem.purge_except(kept)
+
+        self._add_memory_frame_owner(batch, ms_features, key, shrinkage, selection, h, w, device)
+        if not own:
+            return None
+        self.image_feature_store.delete(frame_ti)
+        return unpad(self.network.aggregate(self.last_mask[0], dim=0), self.pad)
 
     def step(self, image: torch.Tensor, mask: torch.Tensor = None, objects: Optional[List[int]] = None, *,
              hard_mask: bool = True, end: bool = False, image_ti_override: bool = None,
@@ -259,7 +362,7 @@ class DEVAInferenceCore:
         if annotated and objects is None:
             assert not hard_mask
             objects = list(range(1, mask.shape[0] + 1))
-        if self.memory._shard_group is not None and self.memory._shard_owner is not None:
+        if self._frame_owner_mode():
             return self._step_frame_owner(image, mask, objects, hard_mask, end, image_ti_override, delete_buffer)
 
         frame_ti, batch, ms_features, key, shrinkage, selection = self._begin_frame(image, image_ti_override)

@@ -19,6 +19,7 @@ gfx950 kernels of libdeva_hip:
 """
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from deva.hip import ops
@@ -134,8 +135,10 @@ class MemoryManager:
         owner=r   : frame-owner mode -- rank r alone runs the encoder / decoder; `DEVAInferenceCore.step`
                     broadcasts the query key / selection from it, the read-out columns are gathered to it
                     only, and on memory frames it broadcasts the new key / shrinkage / selection / value
-                    rows to the other ranks' banks.  Only `step` is routed in this mode
-                    (`incorporate_detection` raises NotImplementedError)."""
+                    rows to the other ranks' banks.  `incorporate_detection` and the semi-online voting
+                    buffer follow the same contract: every rank makes the same calls, rank r alone merges
+                    and votes and broadcasts its decisions (the object table, `broadcast_bytes`), the other
+                    ranks adopt them and return None (the vote: no mask)."""
         import torch.distributed as dist
         self._refuse_sharded_full_softmax(self.top_k, 'shard_queries')
         if not dist.is_initialized():
@@ -168,7 +171,9 @@ class MemoryManager:
         owner=r: additionally frame-owner mode (see `shard_queries`): rank r alone runs the encoder / decoder and
         broadcasts the query and the new memory rows; the partial read-outs are then REDUCED to it (`dist.reduce`,
         half the bytes of the all-reduce every-rank-decodes needs) and nobody else receives them.  The configuration
-        for a bank that outgrows one GPU: every rank stores and scores 1/world of it, one rank decodes."""
+        for a bank that outgrows one GPU: every rank stores and scores 1/world of it, one rank decodes.  Detection frames
+        and the voting buffer work as in `shard_queries(owner=r)`; a purge drops each rank's share of the purged
+        objects' value rows."""
         import torch.distributed as dist
         self._refuse_sharded_full_softmax(self.top_k, 'shard_bank')
         if self.top_k > self.MAX_TOP_K_SHARDED_BANK:
@@ -437,6 +442,22 @@ class MemoryManager:
         dist.broadcast(packed, src=self._owner_global_rank(), group=self._shard_group)
         self.comm_bytes += packed.numel() * 4
         return packed[:ck].view(1, ck, h, w), packed[ck:].view(1, ck, h, w)
+
+    def broadcast_bytes(self, data: Optional[bytes], device) -> bytes:
+        """frame-owner mode: host-side bytes of the owner (the object table after a detection frame, the result of a
+        vote) -> every rank, as an int64 length and then the payload (uint8 on `device`).  The other ranks pass None."""
+        import torch.distributed as dist
+        src = self._owner_global_rank()
+        own = self.is_frame_owner
+        size = torch.tensor([len(data) if own else 0], dtype=torch.int64, device=device)
+        dist.broadcast(size, src=src, group=self._shard_group)
+        n = int(size.item())
+        payload = (torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).to(device) if own
+                   else torch.empty(n, dtype=torch.uint8, device=device))
+        if n:
+            dist.broadcast(payload, src=src, group=self._shard_group)
+        self.comm_bytes += 8 + n
+        return data if own else payload.cpu().numpy().tobytes()
 
     # ------------------------------------------------------------------ write
     def add_memory(self, key: torch.Tensor, shrinkage: torch.Tensor, value: torch.Tensor,

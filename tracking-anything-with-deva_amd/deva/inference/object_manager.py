@@ -2,12 +2,66 @@
 
 Real object ids never change; temporary ids are the 1-based channel positions of the objects in
 the network tensors and are re-packed when objects are removed."""
-from typing import Dict, List, Set, Tuple, Union
+import struct
+from typing import Dict, List, Sequence, Set, Tuple, Union
 
 import numpy as np
 import torch
 
 from deva.inference.object_info import ObjectInfo
+
+# ---------------------------------------------------------------------- byte form (frame-owner mode, several GPUs)
+# Little-endian, no padding.  An object: id (int64), thing flag (uint8: 0 None, 1 False, 2 True), missed-detection
+# counter (int32), then its category votes and its score votes, each as a count (uint32) followed by one entry per
+# vote: a flag byte (0 = None) and, when set, the value (int64 category / float64 score).  21 bytes per object, plus
+# 9 per vote of either list (1 for a None vote).
+_THING_CODE = {None: 0, False: 1, True: 2}
+_THING_OF = {0: None, 1: False, 2: True}
+
+
+def _pack_votes(values: Sequence, fmt: str) -> bytes:
+    out = [struct.pack('<I', len(values))]
+    for v in values:
+        out.append(b'\x00' if v is None else b'\x01' + struct.pack(fmt, v))
+    return b''.join(out)
+
+
+def _unpack_votes(data: bytes, at: int, fmt: str, size: int) -> Tuple[List, int]:
+    (n,), at = struct.unpack_from('<I', data, at), at + 4
+    out = []
+    for _ in range(n):
+        present, at = data[at], at + 1
+        if present:
+            out.append(struct.unpack_from(fmt, data, at)[0])
+            at += size
+        else:
+            out.append(None)
+    return out, at
+
+
+def pack_objects(objects: Sequence[ObjectInfo]) -> bytes:
+    """ObjectInfo list -> bytes (count, then the objects in order; categories travel as int, scores as float)"""
+    out = [struct.pack('<I', len(objects))]
+    for o in objects:
+        out.append(struct.pack('<qBi', int(o.id), _THING_CODE[o.isthing], int(o.poke_count)))
+        out.append(_pack_votes([None if c is None else int(c) for c in o.category_ids], '<q'))
+        out.append(_pack_votes([None if s is None else float(s) for s in o.scores], '<d'))
+    return b''.join(out)
+
+
+def unpack_objects(data: bytes, at: int = 0) -> Tuple[List[ObjectInfo], int]:
+    """inverse of `pack_objects` -> (objects, offset after them)"""
+    (n,), at = struct.unpack_from('<I', data, at), at + 4
+    objects = []
+    for _ in range(n):
+        oid, thing, poke = struct.unpack_from('<qBi', data, at)
+        at += 13
+        o = ObjectInfo(id=oid, isthing=_THING_OF[thing])
+        o.poke_count = poke
+        o.category_ids, at = _unpack_votes(data, at, '<q', 8)
+        o.scores, at = _unpack_votes(data, at, '<d', 8)
+        objects.append(o)
+    return objects, at
 
 
 class ObjectManager:
@@ -135,3 +189,24 @@ class ObjectManager:
 
     def find_object_by_id(self, obj_id) -> ObjectInfo:
         return self.obj_id_to_obj[obj_id]
+
+    # ------------------------------------------------------------------ one clip on several GPUs
+    def encode_state(self) -> bytes:
+        """the whole table as bytes, the same bytes for the same table: use_long_id (1 B), the reserved ids (count +
+        sorted int64), then the objects in tmp-id order (`pack_objects`).  Frame-owner mode: the owner's decisions of a
+        detection frame travel to the other ranks in this form (`DEVAInferenceCore.incorporate_detection`)."""
+        hist = sorted(int(i) for i in self.all_historical_object_ids)
+        objects = [self.tmp_id_to_obj[t] for t in range(1, len(self.tmp_id_to_obj) + 1)]
+        return struct.pack(f'<?I{len(hist)}q', bool(self.use_long_id), len(hist), *hist) + pack_objects(objects)
+
+    def load_state(self, data: bytes, at: int = 0) -> int:
+        """replace this table with the one `encode_state` wrote into `data` at offset `at`; -> offset after it"""
+        use_long_id, n = struct.unpack_from('<?I', data, at)
+        hist = struct.unpack_from(f'<{n}q', data, at + 5)
+        objects, end = unpack_objects(data, at + 5 + 8 * n)
+        self.use_long_id = use_long_id
+        self.all_historical_object_ids = set(hist)
+        self.obj_to_tmp_id = {obj: i + 1 for i, obj in enumerate(objects)}
+        self.tmp_id_to_obj = {i + 1: obj for i, obj in enumerate(objects)}
+        self._reindex()
+        return end
