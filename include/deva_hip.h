@@ -139,6 +139,13 @@ typedef struct deva_conv_desc {
   const float* weight_wino;
 } deva_conv_desc;
 
+/* SIZE LIMITS.  The kernels address each source with 32-bit byte offsets from its base, so one launch takes sources
+ * of fewer than 2^29 floats (2 GiB).  A batch whose in0 or in1 spans more -- (batch - 1) * batch_stride + channels * H * W
+ * floats; the decoder's 256-channel 1/4-scale maps reach that at 81 objects per pass at 480x864, 17 at 1088x1920, 5 at
+ * 2160x3840 -- is NOT refused: deva_conv2d runs it as consecutive sub-batches of the largest image count that stays
+ * below the limit (same kernels per image; the split-K factor of a layer may differ from the unsplit batch's, i.e. fp32
+ * summation order).  Only a SINGLE image whose source reaches 2^29 floats is refused (error: "one image of a source
+ * spans 2 GiB or more"), as is an output of 2^31 pixels or more. */
 int deva_conv2d(const deva_conv_desc* desc, void* stream);
 /* fp16 weights of the amp path (HOST pointers, model load): -> number of uint16 elements (out == NULL: size query),
  * -1 when the layer is not eligible (cin % 64 != 0) or on bad arguments */

@@ -52,7 +52,13 @@ def amp_takes(pc, x0, x1, stride, pad):
     c0, c1 = x0.shape[1], 0 if x1 is None else x1.shape[1]
     h, w = x0.shape[-2:]
     return (pc.weight_f16 is not None and stride == 1 and pc.cout >= 64 and c0 % 64 == 0 and c1 % 64 == 0 and
-            ((pc.kh == 1 and pad == 0) or (pc.kh == 3 and pad == 1)) and (h * w) % 4 == 0 and w >= 4)
+            ((pc.kh == 1 and pad == 0) or (pc.kh == 3 and pad == 1)) and (h * w) % 4 == 0 and w >= 4 and _guard_ok(w, pad))
+
+
+def _guard_ok(w, pad):
+    """the vector gathers need pad * (W + 1) + 4 readable floats around both inputs (deva_conv2d: vec_ok); the tensors of
+    ops._alloc and of the tests' guarded buffers carry ops.GUARD"""
+    return pad * (w + 1) + 4 <= real.GUARD
 
 
 def split_takes(pc, x0, x1, stride, pad):
@@ -63,7 +69,45 @@ def split_takes(pc, x0, x1, stride, pad):
     whole = c0 % 32 == 0 and c1 % 32 == 0
     tail = pc.kh == 1 and (c0 % 32 == 0 if c1 else True)  # 1x1: a partial last K step (513 = 512 + 1 channels) is taken too
     return (pc.weight_split is not None and stride == 1 and pc.cout >= 64 and (whole or tail) and
-            ((pc.kh == 1 and pad == 0) or (pc.kh == 3 and pad == 1)) and (h * w) % 4 == 0 and w >= 4)
+            ((pc.kh == 1 and pad == 0) or (pc.kh == 3 and pad == 1)) and (h * w) % 4 == 0 and w >= 4 and _guard_ok(w, pad))
+
+
+def wino_takes(pc, x0, x1, stride, pad, batch=None):
+    """the shapes the fp32 Winograd kernel takes (csrc/conv_wino.hip: launch_conv_wino + the vector-gather geometry of
+    deva_conv2d), for a call WITHOUT amp / split on guard-banded inputs: 3x3 / stride 1 / pad 1, even width >= 4, a pixel
+    count of 4k, channel counts that are multiples of 8, cout >= 32 and at least 160 workgroups of 64 channels x 64 tiles
+    of 2x2 outputs (odd heights end in a tile row of one output row); rows of at most ops.GUARD - 5 pixels.  batch: of the call (default: the operands')"""
+    c0, c1 = x0.shape[1], 0 if x1 is None else x1.shape[1]
+    h, w = x0.shape[-2:]
+    if batch is None:
+        batch = max(x0.shape[0], 1 if x1 is None else x1.shape[0])
+    if not (pc.weight_wino is not None and pc.kh == 3 and pc.kw == 3 and stride == 1 and pad == 1 and pc.cout >= 32):
+        return False
+    if w % 2 or w < 4 or (h * w) % 4 or c0 % 8 or c1 % 8 or not _guard_ok(w, pad):
+        return False
+    tiles = batch * ((h + 1) // 2) * (w // 2)
+    return ((pc.cout + 63) // 64) * ((tiles + 63) // 64) >= 160
+
+
+CONV_SPAN_LIMIT = 1 << 29  # floats one launch of deva_conv2d addresses inside a source (32-bit byte offsets)
+
+
+def conv_sub_batches(batch, c0, hw, stride0, c1=0, stride1=0):
+    """the sub-batches deva_conv2d runs a call as (csrc/conv_igemm.hip, the block in front of ConvArgs): a source spans
+    (batch - 1) * batch_stride + channels * H * W floats; a batch that reaches CONV_SPAN_LIMIT is cut into runs of the
+    largest image count below it.  -> list of image counts; raises where the library refuses (one image too large)"""
+    lim = CONV_SPAN_LIMIT - 1
+    span0 = (batch - 1) * stride0 + c0 * hw
+    span1 = (batch - 1) * stride1 + c1 * hw if c1 else 0
+    per = batch
+    if (span0 > lim or span1 > lim) and batch > 1:
+        if stride0 > 0:
+            per = min(per, (lim - c0 * hw) // stride0 + 1)
+        if c1 and stride1 > 0:
+            per = min(per, (lim - c1 * hw) // stride1 + 1)
+    if per < 1 or c0 * hw > lim or c1 * hw > lim:
+        raise real.DevaHipError('one image of a source spans 2 GiB or more')
+    return [min(per, batch - b0) for b0 in range(0, batch, per)]
 
 
 _SPLIT_FALLBACKS = [0]
@@ -126,8 +170,21 @@ def stem7x7(ps, image, masks=None, relu=False):
     return F.relu(y) if relu else y
 
 
-def upsample2x_add_ds2(x, skip):
-    return upsample2x_add(x, skip), area_downsample(x, 2)
+def upsample2x_add_ds2(x, skip, out=None):
+    return upsample2x_add(x, skip, out), area_downsample(x, 2)
+
+
+def upsample2x_add_map(x, skip, skip_index, out=None):
+    # contract of deva_upsample2x_add_map: item b is the broadcast op with skip[skip_index[b]]
+    y = F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False) + skip[skip_index.long()]
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y
+
+
+def upsample2x_add_ds2_map(x, skip, skip_index):
+    return upsample2x_add_map(x, skip, skip_index), area_downsample(x, 2)
 
 
 def pad2d(x, pad):
@@ -152,9 +209,13 @@ def maxpool3x3s2(x, relu_after=False):
     return F.relu(y) if relu_after else y
 
 
-def upsample2x_add(x, skip):
+def upsample2x_add(x, skip, out=None):
     y = F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=False)
-    return y if skip is None else skip + y
+    y = y if skip is None else skip + y
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y
 
 
 def area_downsample(x, factor):

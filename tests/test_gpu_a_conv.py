@@ -516,3 +516,194 @@ def test_split_k_is_deterministic(cin, cout, k, h, w):
     torch.cuda.synchronize()
     bad = sum(int(not torch.equal(o, first)) for o in outs)
     assert bad == 0, f'{bad} of 300 repetitions differ from the first result'
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# A seeded geometry sweep over the dispatcher (deva_conv2d, launch_conv_q4, launch_conv_wino, launch_conv_f16, the two
+# cout == 1 kernels).  The case list is GENERATED (fixed seed; the id spells the case out): per kernel family the generator
+# crosses the map geometries on which kernels go wrong -- odd x odd, even x odd, odd x even, width 4k + 2 (quads wrap rows),
+# width < 4, height 1, a prime pixel count, and a friendly control -- with batch 1 / 3, a broadcast first source, ReLU on
+# load, residual none / full / broadcast and every activation, at sizes taken from the dispatcher's own thresholds so that
+# each family is reached on both sides of its rule (tests/test_geometry_rules_cpu.py counts that, without a GPU).
+GEO_CLASSES = ('oddxodd', 'evenxodd', 'oddxeven', 'w4k+2', 'w<4', 'h1', 'prime', 'friendly')
+
+
+def _odd(n):
+    return max(1, int(n) | 1)
+
+
+def _next_prime(n):
+    n = max(2, int(n))
+    while any(n % p == 0 for p in range(2, int(n**0.5) + 1)):
+        n += 1
+    return n
+
+
+def _geo(cls, px):
+    """(H, W) of a map of class `cls` with about px pixels"""
+    side = max(2.0, (px * 1.6)**0.5)
+    if cls == 'oddxodd':
+        w = _odd(side)
+        return _odd(px / w), w
+    if cls == 'evenxodd':
+        w = max(5, _odd(side))
+        return max(2, int(px / w) // 2 * 2), w
+    if cls == 'oddxeven':  # a pixel count of 4k with an odd height (45 x 80): Winograd's tile row of one output row
+        w = max(4, int(side) // 4 * 4)
+        return _odd(px / w), w
+    if cls == 'w4k+2':
+        w = max(6, int(side) // 4 * 4 + 2)
+        return max(2, int(px / w) // 2 * 2), w
+    if cls == 'w<4':
+        return max(2, int(px / 3) // 2 * 2 + (px // 7) % 2), 3 if px % 2 else 2
+    if cls == 'h1':
+        return 1, max(4, int(px) // 4 * 4)
+    if cls == 'prime':
+        return _next_prime(px), 1
+    w = max(8, int(side) // 8 * 8)
+    return max(2, int(px / w) // 2 * 2), w
+
+
+# (family, mode, k, c0, c1, cout, pixels over the whole batch, geometry classes)
+_ALL = GEO_CLASSES
+_SWEEP_FAMILIES = [
+    # fp32 MFMA tiles (csrc/conv_mfma.hip: launch_conv_q4): cout <= 32 -> 32x128
+    ('tile32', 'fp32', 3, 48, 0, 24, 700, _ALL), ('tile32', 'fp32', 1, 40, 8, 32, 700, ('oddxodd', 'w4k+2', 'friendly')),
+    # 64x64: two K-slice groups (18 K steps, few tiles) / none (4 K steps)
+    ('tile64', 'fp32', 3, 64, 0, 72, 400, _ALL), ('tile64', 'fp32', 1, 96, 32, 96, 400, ('oddxodd', 'evenxodd', 'h1', 'friendly')),
+    # 64x64 with four K-slice groups (>= 32 K steps, 64 .. 208 tiles) and global split-K below 192 tiles
+    ('kslice4', 'fp32', 3, 128, 0, 128, 3000, _ALL),
+    ('splitk', 'fp32', 1, 1024, 0, 256, 1620, ('oddxodd', 'w4k+2', 'h1', 'friendly', 'prime')),
+    ('no_splitk', 'fp32', 1, 1024, 0, 256, 3400, ('oddxodd', 'friendly')),  # >= 192 tiles of 64x64: K slices, no split
+    # 128x128: from 192 tiles up (two K-slice groups up to 256 tiles on the vector kinds); the same layer on fewer pixels -> 64x64
+    ('tile128', 'fp32', 3, 64, 0, 256, 13000, _ALL), ('tile128_big', 'fp32', 3, 64, 0, 256, 17500, ('oddxodd', 'friendly')),
+    ('tile128_switch', 'fp32', 3, 64, 0, 256, 6000, ('oddxodd', 'w4k+2', 'friendly')),
+    # Winograd (csrc/conv_wino.hip): even width, 4k pixels, >= 160 workgroups of 64 channels x 64 tiles
+    ('wino', 'wino', 3, 64, 0, 128, 21000, _ALL), ('wino', 'wino', 3, 32, 40, 192, 14200, _ALL),
+    ('wino_small', 'wino', 3, 64, 0, 128, 9000, ('friendly', 'oddxeven')),  # below the 160 workgroups
+    # --amp / --f16_split (csrc/conv_f16.hip): 4k pixels and width >= 4; channel counts of 64 / 32
+    ('amp', 'amp', 3, 64, 0, 64, 520, _ALL), ('amp', 'amp', 1, 64, 64, 96, 520, _ALL),
+    ('amp_channels', 'amp', 3, 96, 0, 64, 520, ('friendly', 'w4k+2')),
+    ('split', 'split', 3, 64, 32, 96, 520, _ALL), ('split', 'split', 1, 64, 1, 128, 520, _ALL),
+    ('split_channels', 'split', 3, 48, 0, 96, 520, ('friendly', 'w4k+2')),
+    # cout == 1 (csrc/conv_cout1.hip): the row-reusing 3x3 kernel from 16 384 pixels (width 4k), the table kernel below them
+    # for K <= 7168, the MFMA tile for everything else
+    ('cout1_rows', 'fp32', 3, 32, 0, 1, 16900, ('friendly', 'oddxeven', 'h1', 'oddxodd', 'w4k+2')),
+    ('cout1_table', 'fp32', 3, 40, 8, 1, 600, _ALL),
+    ('cout1_mfma', 'fp32', 3, 800, 0, 1, 300, ('friendly', 'oddxodd')),
+]
+_ACT_NAMES = {ops.ACT_NONE: 'none', ops.ACT_RELU: 'relu', ops.ACT_SIGMOID: 'sigmoid', ops.ACT_SQUARE_PLUS_ONE: 'sq1'}
+
+
+def _sweep_cases():
+    """-> [(id, family, mode, c0, c1, cout, k, stride, pad, batch, H, W, bcast0, relu_in, residual, act, bias, out_shift)]"""
+    import random
+    rng = random.Random(20240607)
+    acts = list(_ACT_NAMES)
+    cases, i = [], 0
+    for family, mode, k, c0, c1, cout, px, classes in _SWEEP_FAMILIES:
+        for cls in classes:
+            batch = (1, 3)[i % 2]
+            if cls == 'h1' and px > 8000:
+                batch = 3  # one row wider than the guard bands (ops.GUARD floats) leaves the vector gathers: keep it below
+            H, W = _geo(cls, max(1, px // batch))
+            bcast0 = batch > 1 and c1 > 0 and rng.random() < 0.5
+            relu_in = rng.random() < 0.5
+            res = ('none', 'full', 'bcast')[i % 3] if batch > 1 else ('none', 'full')[i % 2]
+            act = acts[(i // 2) % 4]
+            bias = rng.random() < 0.8
+            # a few stride-2 layers among the plain fp32 tiles (the scalar gather either way)
+            stride = 2 if (mode == 'fp32' and family in ('tile32', 'tile64') and cls in ('oddxodd', 'evenxodd') and H > 2) else 1
+            out_shift = 1 if i % 5 == 4 else 0  # every 5th case writes through a view 4 bytes off 16: no LDS output stage
+            cid = (f'{family}-{k}x{k}s{stride}-{c0}+{c1}to{cout}-{cls}-b{batch}x{H}x{W}' + ('-bcast0' if bcast0 else '') +
+                   ('-reluin' if relu_in else '') + f'-res_{res}-{_ACT_NAMES[act]}' + ('' if bias else '-nobias') +
+                   ('-outoff' if out_shift else ''))
+            cases.append((cid, family, mode, c0, c1, cout, k, stride, k // 2, batch, H, W, bcast0, relu_in, res, act, bias, out_shift))
+            i += 1
+    return cases
+
+
+SWEEP = _sweep_cases()
+
+
+def sweep_takes(case):
+    """what the eligibility predicates of tests/emu_ops.py say about a sweep case (shapes only; no library, no GPU)"""
+    from types import SimpleNamespace
+    cid, family, mode, c0, c1, cout, k, stride, pad, batch, H, W, bcast0 = case[:13]
+    cin = c0 + c1
+    pc = SimpleNamespace(kh=k, kw=k, cout=cout, weight_f16=True if (cin % 64 == 0 and cout > 1) else None,
+                         weight_split=True if (not (cin % 32 and k > 1) and cout > 1) else None,
+                         weight_wino=True if (k == 3 and cin % 8 == 0) else None)
+    x0 = torch.empty(batch, c0, H, W, device='meta')
+    x1 = torch.empty(batch, c1, H, W, device='meta') if c1 else None
+    return dict(amp=emu_ops.amp_takes(pc, x0, x1, stride, pad), split=emu_ops.split_takes(pc, x0, x1, stride, pad),
+                wino=emu_ops.wino_takes(pc, x0, x1, stride, pad, batch))
+
+
+_SWEEP_WORST = {}
+
+
+@pytest.mark.parametrize('case', SWEEP, ids=[c[0] for c in SWEEP])
+def test_conv_geometry_sweep(case):
+    """every case with NaN-poisoned guard bands around both inputs, written through `out=` into a view whose surroundings
+    hold a sentinel.  Bounds (this file's, unchanged): 2e-5 of the output range against the fp32 CPU convolution (--amp:
+    against the convolution of the fp16-rounded operands); against fp64, e <= 2 e_f32 + 1e-6 where the split kernels take
+    the case and e_w <= 8 e_d + 1e-6 where the Winograd kernel does, e_f32 / e_d from the direct fp32 kernels on the same case"""
+    cid, family, mode, c0, c1, cout, k, stride, pad, batch, H, W, bcast0, relu_in, res, act, bias, out_shift = case
+    g = torch.Generator().manual_seed(zlib.crc32(cid.encode()) % 100000)
+    cin = c0 + c1
+    w = rand(g, cout, cin, k, k, scale=(2.0 / (cin * k * k))**0.5)
+    b = rand(g, cout, scale=0.1) if bias else None
+    pc = ops.pack_conv(w, b, None, amp=mode == 'amp', split=mode == 'split', wino=mode == 'wino')
+    pc_direct = ops.pack_conv(w, b, None)
+    x0 = rand(g, 1 if bcast0 else batch, c0, H, W)
+    x1 = rand(g, batch, c1, H, W) if c1 else None
+    oh, ow = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    residual = rand(g, batch if res == 'full' else 1, cout, oh, ow) if res != 'none' else None
+    takes = sweep_takes(case)
+    assert takes['amp'] == emu_ops.amp_takes(pc, x0, x1, stride, pad) or mode != 'amp'
+    assert takes['split'] == emu_ops.split_takes(pc, x0, x1, stride, pad) or mode != 'split'
+    assert takes['wino'] == emu_ops.wino_takes(pc, x0, x1, stride, pad, batch) or mode != 'wino'
+    taken = mode != 'fp32' and takes[mode]
+    kw = dict(stride=stride, pad=pad, relu_in=relu_in, residual=residual, act=act)
+    want = emu_ops.conv2d(pc, x0, x1, amp=mode == 'amp', **kw)
+    want64 = _conv64(pc_direct, x0, x1, stride, pad, relu_in, residual, act)
+    # the output: a view inside a buffer of sentinels, 16-byte aligned or 4 bytes further on
+    n_out, sentinel = batch * cout * oh * ow, 12345.0
+    buf = torch.full((n_out + 2 * ops.GUARD + 4,), sentinel, device=dev())
+    lo = ops.GUARD + out_shift
+    out = buf[lo:lo + n_out].view(batch, cout, oh, ow)
+    dkw = dict(kw, residual=to_dev(residual))
+    before = ops.split_fallbacks(dev())
+    got = ops.conv2d(to_dev(pc), _guarded(x0), _guarded(x1), out=out, amp=mode == 'amp', split=mode == 'split', **dkw)
+    direct = ops.conv2d(to_dev(pc_direct), _guarded(x0), _guarded(x1), **dkw)
+    torch.cuda.synchronize()
+    assert got.data_ptr() == out.data_ptr() and got.shape == want.shape
+    assert bool((buf[:lo] == sentinel).all()) and bool((buf[lo + n_out:] == sentinel).all()), f'{cid}: wrote outside its output'
+    assert not torch.isnan(got).any(), f'{cid}: guard-band values leaked into the result'
+    assert ops.split_fallbacks(dev()) == before
+    scale, scale64 = max(1.0, want.abs().max().item()), max(1e-30, want64.abs().max().item())
+    err = max_err(got, want)
+    e_got = (got.double().cpu() - want64).abs().max().item() / scale64
+    e_dir = (direct.double().cpu() - want64).abs().max().item() / scale64
+    print(f'{cid}: taken={taken} max abs err {err:.3e} (|ref|max {scale:.3e}); against fp64 / |ref|max: {e_got:.3e}, direct '
+          f'fp32 kernels {e_dir:.3e}')
+    worst = _SWEEP_WORST.setdefault(family, [0.0, 0.0])
+    worst[0], worst[1] = max(worst[0], err / scale), max(worst[1], e_got / max(e_dir, 1e-30) if taken and mode != 'amp' else 0.0)
+    assert err <= 2e-5 * scale, (cid, err)
+    assert max_err(direct, emu_ops.conv2d(pc_direct, x0, x1, **kw)) <= 2e-5 * scale, (cid, 'direct kernels')
+    if mode == 'split' and taken:
+        assert e_got <= 2.0 * e_dir + 1e-6, (cid, e_got, e_dir)
+    if mode == 'wino' and taken:
+        if os.environ.get('DEVA_TEST_DRYRUN') != '1':  # (the emulated ops have one convolution)
+            assert not torch.equal(got, direct), f'{cid}: the Winograd kernel did not run (bit-identical to the direct kernels)'
+        assert e_got <= 8.0 * e_dir + 1e-6, (cid, e_got, e_dir)
+    if mode == 'amp':
+        exact = emu_ops.conv2d(pc, x0, x1, **kw)
+        assert (max_err(want, exact) > 0) == bool(taken), f'{cid}: the fp16 rounding of the reference and the rule disagree'
+
+
+def test_conv_geometry_sweep_report():
+    """the sweep's worst figures per family (printed for DESIGN section 2; asserted case by case above)"""
+    for family, (rel, ratio) in sorted(_SWEEP_WORST.items()):
+        print(f'sweep {family}: worst max-abs err / |ref|max {rel:.2e}' + (f', worst ratio to the direct kernels against fp64 {ratio:.2f}' if ratio else ''))

@@ -183,3 +183,119 @@ def test_pad2d_matches_f_pad(dtype, shape, pad):
     ref, p_ref = pad_divide_by(x, 16)
     assert p == p_ref and torch.equal(via.cpu(), ref)
 
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Vector-versus-scalar identity (each 16-byte form is "bit-identical, asserted against the scalar
+# forms").  The layers of four frames whose 1/16 maps are 30x45, 29x53, 54x30 and 45x80 (tests/test_gpu_m_geometry.py), at
+# their object counts: the same data through a 16-byte-aligned view and through a view 4 bytes further on must give
+# torch.equal results, and both must meet the emu_ops contract at this file's tolerances.  Every input sits inside a
+# buffer filled with +inf on one run and -inf on the other: NaN does not survive fmaxf, so a NaN poison would not show a
+# max-pool over-read; an infinity of either sign survives every kernel here as inf or NaN.
+FRAMES = [(480, 720, 2), (464, 848, 1), (864, 480, 3), (720, 1280, 2)]
+POISONS = [float('inf'), float('-inf')]
+_PAD = 4096  # floats of poison on either side of a view (a multiple of 4: the aligned view stays aligned)
+
+
+def _views(x, poison):
+    """(16-byte aligned view, view 4 bytes further on) of the same values on the device, each inside a poisoned buffer"""
+    out = []
+    for shift in (0, 1):
+        buf = torch.full((x.numel() + 2 * _PAD + 4,), poison, device=dev())
+        view = buf[_PAD + shift:_PAD + shift + x.numel()].view(*x.shape)
+        view.copy_(x)
+        assert dev().type == 'cpu' or view.data_ptr() % 16 == 4 * shift
+        out.append(view)
+    return out
+
+
+def _identical(name, results, want, tol):
+    """results: the same op over differently aligned views of the same data"""
+    torch.cuda.synchronize()
+    for r in results[1:]:
+        assert torch.equal(results[0], r), f'{name}: the vector and the scalar kernel differ'
+    for r in results:
+        assert bool(torch.isfinite(r).all()), f'{name}: poison from outside the tensor reached the result'
+        _check(name, r, want, tol)
+
+
+@pytest.mark.parametrize('poison', POISONS, ids=['+inf', '-inf'])
+@pytest.mark.parametrize('H,W,no', FRAMES)
+def test_maxpool_vector_path_is_bit_identical_to_the_scalar_kernel(H, W, no, poison):
+    """the value encoder's pool on the stem output (1/2 scale: 240x360, 232x424, 432x240, 360x640 -- widths of 8k, so the
+    aligned view runs four outputs per thread), ReLU after it for every other frame"""
+    x = rand(torch.Generator().manual_seed(H + W), no, 64, H // 2, W // 2)
+    relu = bool(no % 2)
+    _identical(f'maxpool {tuple(x.shape)}', [ops.maxpool3x3s2(v, relu) for v in _views(x, poison)],
+               emu_ops.maxpool3x3s2(x, relu), 0)
+
+
+def _up_cases():
+    cases = []
+    for H, W, no in FRAMES:
+        cases.append((no, 256, H // 16, W // 16))  # 1/16 -> 1/8: 30x45 and 29x53 have odd widths (scalar kernel either way)
+        cases.append((no, 64, H // 8, W // 8))     # 1/8 -> 1/4: even sizes, also with the fused x0.5 output
+    # the quad kernel runs one grid row per plane: up to 65 535 planes
+    return cases + [(255, 257, 3, 4), (256, 256, 3, 4)]
+
+
+@pytest.mark.parametrize('poison', POISONS, ids=['+inf', '-inf'])
+@pytest.mark.parametrize('shape', _up_cases(), ids=lambda s: 'x'.join(map(str, s)))
+def test_upsample2x_vector_path_is_bit_identical_to_the_scalar_kernel(shape, poison):
+    """x2 up-sampling (+ skip, + the fused x0.5 output, + the per-item skip map): the switch looks at `out` and `skip`, not
+    at the input -- an offset OUTPUT view (out=) or an offset skip sends the call to the scalar kernel"""
+    b, c, h, w = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    x, skip = rand(g, *shape), rand(g, 1, c, 2 * h, 2 * w)
+    want = emu_ops.upsample2x_add(x, skip)
+    xa, xo = _views(x, poison)
+    sa, so = _views(skip, poison)
+    oa, oo = _views(torch.zeros(b, c, 2 * h, 2 * w), poison)
+    res = [ops.upsample2x_add(xa, sa), ops.upsample2x_add(xo, sa), ops.upsample2x_add(xa, sa, out=oa),
+           ops.upsample2x_add(xa, sa, out=oo), ops.upsample2x_add(xa, so)]
+    assert res[2].data_ptr() == oa.data_ptr() and res[3].data_ptr() == oo.data_ptr()
+    _identical(f'up2x+skip {shape}', res, want, 1e-5)
+    _identical(f'up2x {shape}', [ops.upsample2x_add(xa, None), ops.upsample2x_add(xa, None, out=oo)],
+               emu_ops.upsample2x_add(x, None), 1e-5)
+    if h % 2 == 0 and w % 2 == 0:
+        (ua, da), (uo, do) = ops.upsample2x_add_ds2(xa, sa), ops.upsample2x_add_ds2(xo, sa, out=oo)
+        _identical(f'up2x+ds2 {shape}', [ua, uo, res[0]], want, 1e-5)
+        _identical(f'ds2 {shape}', [da, do], emu_ops.area_downsample(x, 2), 1e-5)
+    if b <= 3:
+        skips = rand(g, 2, c, 2 * h, 2 * w)
+        index = ops.clip_index([1, 0, 1][:b], 2, dev())
+        want_m = torch.cat([emu_ops.upsample2x_add(x[i:i + 1], skips[s:s + 1]) for i, s in enumerate([1, 0, 1][:b])], 0)
+        ma, _ = _views(skips, poison)
+        _identical(f'up2x+map {shape}', [ops.upsample2x_add_map(xa, ma, index), ops.upsample2x_add_map(xa, ma, index, out=oo)],
+                   want_m, 1e-5)
+    for buf in (oa, oo):  # what the kernels wrote stayed inside the output views
+        flat, off = buf._base, buf.storage_offset()
+        assert bool((flat[:off] == poison).all()) and bool((flat[off + buf.numel():] == poison).all())
+
+
+@pytest.mark.parametrize('poison', POISONS, ids=['+inf', '-inf'])
+@pytest.mark.parametrize('H,W,no', FRAMES)
+def test_cbam_apply_vector_path_is_bit_identical_to_the_scalar_kernel(H, W, no, poison):
+    """the fuser's CBAM at 1/16 (512 channels): pooling, MLP and the 7x7 gate do not look at the alignment; the final
+    x + x * scale * sigmoid(gate) runs four pixels per thread on aligned maps of 4k pixels (54x30, 45x80) only"""
+    b, c, h, w = no, 512, H // 16, W // 16
+    g = torch.Generator().manual_seed(H + W + 6)
+    x = rand(g, b, c, h, w)
+    hid = c // 16
+    w1, b1 = rand(g, hid, c, scale=c**-0.5), rand(g, hid, scale=0.1)
+    w2, b2 = rand(g, c, hid, scale=hid**-0.5), rand(g, c, scale=0.1)
+    sp = ops.pack_conv(rand(g, 1, 2, 7, 7, scale=0.2), rand(g, 1, scale=0.1))
+    args = [to_dev(t) for t in (w1, b1, w2, b2, sp)]
+    _identical(f'cbam {(b, c, h, w)}', [ops.cbam(v, *args) for v in _views(x, poison)], emu_ops.cbam(x, w1, b1, w2, b2, sp), 1e-5)
+
+
+@pytest.mark.parametrize('poison', POISONS, ids=['+inf', '-inf'])
+@pytest.mark.parametrize('H,W,no', FRAMES)
+def test_gru_gate_vector_path_is_bit_identical_to_the_scalar_kernel(H, W, no, poison):
+    """the sensory update at 1/16: values [no, 1536, h, w], state [no, 512, h, w]; either operand off 16 bytes -> scalar"""
+    b, c, h, w = no, 512, H // 16, W // 16
+    g = torch.Generator().manual_seed(H + W + 7)
+    v, hh = rand(g, b, 3 * c, h, w, scale=2.0), rand(g, b, c, h, w)
+    (va, vo), (ha, ho) = _views(v, poison), _views(hh, poison)
+    _identical(f'gru {(b, c, h, w)}', [ops.gru_update(va, ha), ops.gru_update(vo, ha), ops.gru_update(va, ho)],
+               emu_ops.gru_update(v, hh), 2e-6)

@@ -836,7 +836,7 @@ extern "C" int deva_conv2d(const deva_conv_desc* d, void* stream) {
   if (a.k_layout & DEVA_KLAYOUT_Q4) {
     // buffer addressing: 32-bit byte offsets from the tensor bases
     DEVA_REQUIRE(a.in0_span < (1ll << 29) && a.in1_span < (1ll << 29),
-                 "deva_conv2d: k-quad weights need inputs below 2 GiB (32-bit buffer offsets)");
+                 "deva_conv2d: one image of a source spans 2 GiB or more (32-bit buffer offsets; larger BATCHES run as sub-batches)");
     if (a.gate) {  // the re-run behind a split launch: a persistent kernel (what it costs is its dispatch)
       const int rc = launch_conv_q4_gated(a, st);
       if (rc >= 0) return rc;

@@ -425,8 +425,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WK, (KIND <= 1 || MINW < 2
     };
 
     // ROW: 3-bit validity (dx = 0..2) of this lane's pixel for the dy of K step t; the lane's read base of a step is its
-    // own column (+ dx) or, when the tap falls into the zero padding, the zero column
-    auto taps_of = [&](int t) { return (cmask >> (t % 9 / 3 * 3)) & 7u; };
+    // own column (+ dx) or, when the tap falls into the zero padding, the zero column.  Steps from ks_end on (a K-slice
+    // group with fewer steps than the loop walks) read the zero column throughout: their weights are zeros, but the row tile
+    // in LDS is the one of step ks_last, whose dy is not the dy of t -- a tap that is valid for t may sit in the guard band
+    // there, and 0 x (NaN or inf from the guard band) is NaN
+    auto taps_of = [&](int t) { return t < ks_end ? (cmask >> (t % 9 / 3 * 3)) & 7u : 0u; };
     unsigned m3 = ROW ? taps_of(ks0) : 0u;
     const float* b_cur = ROW ? ((m3 & 1u) ? b_rd0 : b_zero0) : b_rd0;  // read base of the current step
 

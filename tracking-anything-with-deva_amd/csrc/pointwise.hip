@@ -149,6 +149,26 @@ __device__ __forceinline__ float bilerp(const float* __restrict__ src, int W, co
   return ly.w0 * top + ly.w1 * bot;
 }
 
+// The x2 up-sampling's interpolation with its roundings spelled out.  Written as `w0 * a + w1 * b` the compiler chose per
+// kernel, and inside the quad kernel per unrolled lane, which product to fuse into the sum; with weights of 1/4 and 3/4 that
+// decides whether the 3/4 product is rounded on its own, so the scalar kernel and the quad kernel below, meant to be the
+// same arithmetic, differed in the last bit (found by test_upsample2x_vector_path_is_bit_identical_to_the_scalar_kernel).
+// Both now go through up2x_pixel, which fixes the fused product per (output row parity, output column % 4) -- to the
+// choices the quad kernel of the earlier builds computed with, measured lane by lane, so that results on the shapes the
+// quad kernel takes do not move: bit 4 * (row is even) + (column % 4) of UP2X_TOP_F1 / UP2X_BOT_F1 set: the interpolation of
+// the upper / lower input row is fma(w0, a, w1 * b), clear: fma(w1, b, w0 * a); across rows always fma(wy0, top, wy1 * bot).
+constexpr unsigned UP2X_TOP_F1 = 0xac, UP2X_BOT_F1 = 0xa4;
+__device__ __forceinline__ float up2x_lerp(bool f1, float w0, float a, float w1, float b) {
+  return f1 ? __builtin_fmaf(w0, a, w1 * b) : __builtin_fmaf(w1, b, w0 * a);
+}
+__device__ __forceinline__ float up2x_pixel(float s00, float s01, float s10, float s11, const Lerp& ly, const Lerp& lx, int oy,
+                                            int ox) {
+  const int lane = ((oy & 1) ? 0 : 4) + (ox & 3);
+  const float top = up2x_lerp((UP2X_TOP_F1 >> lane) & 1u, lx.w0, s00, lx.w1, s01);
+  const float bot = up2x_lerp((UP2X_BOT_F1 >> lane) & 1u, lx.w0, s10, lx.w1, s11);
+  return __builtin_fmaf(ly.w0, top, ly.w1 * bot);
+}
+
 // MAP (deva_upsample2x_add_map): skip holds S planes-of-C and plane b*C + c adds skip plane skip_index[b]*C + c; without
 // MAP skip is one [C][2h][2w] block broadcast over the batch (skip_index unused)
 template <bool MAP>
@@ -163,7 +183,8 @@ __global__ void upsample2x_add_kernel(const float* __restrict__ in, const float*
     const int64_t plane = t / OH;  // b*C + c
     const int c = (int)(plane % C);
     const Lerp ly = lerp_index(oy, 0.5f, h), lx = lerp_index(ox, 0.5f, w);
-    float v = bilerp(in + plane * (int64_t)h * w, w, ly, lx);
+    const float* src = in + plane * (int64_t)h * w;
+    float v = up2x_pixel(src[ly.i0 * w + lx.i0], src[ly.i0 * w + lx.i1], src[ly.i1 * w + lx.i0], src[ly.i1 * w + lx.i1], ly, lx, oy, ox);
     const int64_t sc = MAP ? (int64_t)skip_index[plane / C] * C + c : (int64_t)c;
     if (skip) v = skip[(sc * OH + oy) * OW + ox] + v;
     out[i] = v;
@@ -176,7 +197,7 @@ __global__ void upsample2x_add_kernel(const float* __restrict__ in, const float*
 // one-row form of round 4 issued 10 per 16 bytes (eight scalar loads): that kernel ran at 2.7 TB/s at 1080p / 11 objects,
 // bound by the CU's address path (a vector-memory instruction costs the same whatever its width).  The column window is
 // shifted inside the row at both ends (no read outside the row) and the clamped neighbours are picked from it.  Same
-// per-pixel arithmetic as upsample2x_add_kernel (lerp_index weights, top / bottom order): bit-identical results.
+// per-pixel arithmetic as upsample2x_add_kernel (lerp_index weights, up2x_pixel): bit-identical results.
 // ds2 (optional, h and w even): the 2x2 box means of `in` -- area_downsample(in, 2), the decoder's p8 -> 1/16 for the sensory
 // update (modules.py:121-151) -- written by the threads whose two input rows and inner two columns ARE such a box (odd P):
 // no extra loads, the same sum in the same order as area_downsample_kernel, and one pass over `in` less.
@@ -223,9 +244,7 @@ __global__ __launch_bounds__(256) void upsample2x_add_quad_kernel(const float* _
       // columns of the four outputs: (2j-1, 2j), (2j, 2j+1), (2j, 2j+1), (2j+1, 2j+2) -- clamped like lerp_index clamps
       const float t0 = e == 0 ? a0 : (e == 3 ? c0 : b0), t1 = e == 0 ? b0 : (e == 3 ? d0 : c0);
       const float u0 = e == 0 ? a1 : (e == 3 ? c1 : b1), u1 = e == 0 ? b1 : (e == 3 ? d1 : c1);
-      const float top = lx.w0 * t0 + lx.w1 * t1;
-      const float bot = lx.w0 * u0 + lx.w1 * u1;
-      v[e] = ly.w0 * top + ly.w1 * bot;
+      v[e] = up2x_pixel(t0, t1, u0, u1, ly, lx, oy, e);  // (column 4 j + e)
     }
     const int64_t ofs = ((int64_t)plane * OH + oy) * OW + 4 * j;
     up_f32x4 r = {v[0], v[1], v[2], v[3]};

@@ -473,24 +473,34 @@ def maxpool3x3s2(x: torch.Tensor, relu_after: bool = False) -> torch.Tensor:
     return out
 
 
-def upsample2x_add(x: torch.Tensor, skip: Optional[torch.Tensor]) -> torch.Tensor:
-    """x [B,C,h,w] -> [B,C,2h,2w] bilinear (+ skip [1,C,2h,2w] broadcast over B)"""
+def _up2x_out(out: Optional[torch.Tensor], shape, device, what: str) -> torch.Tensor:
+    if out is None:
+        return _alloc(shape, device)
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise DevaHipError(f'{what}: out must be a contiguous {tuple(shape)}')
+    return out
+
+
+def upsample2x_add(x: torch.Tensor, skip: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B,C,h,w] -> [B,C,2h,2w] bilinear (+ skip [1,C,2h,2w] broadcast over B); out: where to write (default: a new
+    guard-banded tensor)"""
     b, c, h, w = x.shape
     if skip is not None and tuple(skip.shape[-3:]) != (c, 2 * h, 2 * w):
         raise DevaHipError('upsample2x_add: skip shape mismatch')
-    out = _alloc((b, c, 2 * h, 2 * w), x.device)
+    out = _up2x_out(out, (b, c, 2 * h, 2 * w), x.device, 'upsample2x_add')
     check(lib().deva_upsample2x_add(_p(x), _p(skip), _p(out), b, c, h, w, _stream()), 'deva_upsample2x_add')
     return out
 
 
-def upsample2x_add_ds2(x: torch.Tensor, skip: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+def upsample2x_add_ds2(x: torch.Tensor, skip: Optional[torch.Tensor],
+                       out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(upsample2x_add(x, skip), area_downsample(x, 2)) from one pass over x (deva_upsample2x_add_ds2); x [B,C,h,w], h, w even"""
     b, c, h, w = x.shape
     if skip is not None and tuple(skip.shape[-3:]) != (c, 2 * h, 2 * w):
         raise DevaHipError('upsample2x_add_ds2: skip shape mismatch')
     if h % 2 or w % 2:
         raise DevaHipError('upsample2x_add_ds2: even input size expected')
-    out = _alloc((b, c, 2 * h, 2 * w), x.device)
+    out = _up2x_out(out, (b, c, 2 * h, 2 * w), x.device, 'upsample2x_add_ds2')
     ds2 = _alloc((b, c, h // 2, w // 2), x.device)
     check(lib().deva_upsample2x_add_ds2(_p(x), _p(skip), _p(out), _p(ds2), b, c, h, w, _stream()), 'deva_upsample2x_add_ds2')
     return out, ds2
@@ -514,10 +524,11 @@ def _map_args(x: torch.Tensor, skip: torch.Tensor, skip_index: torch.Tensor, wha
     return b, c, h, w
 
 
-def upsample2x_add_map(x: torch.Tensor, skip: torch.Tensor, skip_index: torch.Tensor) -> torch.Tensor:
+def upsample2x_add_map(x: torch.Tensor, skip: torch.Tensor, skip_index: torch.Tensor,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [B,C,h,w] -> [B,C,2h,2w] bilinear + skip[skip_index[b]] (skip [S,C,2h,2w]; skip_index from `clip_index`)"""
     b, c, h, w = _map_args(x, skip, skip_index, 'upsample2x_add_map')
-    out = _alloc((b, c, 2 * h, 2 * w), x.device)
+    out = _up2x_out(out, (b, c, 2 * h, 2 * w), x.device, 'upsample2x_add_map')
     check(lib().deva_upsample2x_add_map(_p(x), _p(skip), _p(skip_index, torch.int32), _p(out), b, c, h, w, _stream()),
           'deva_upsample2x_add_map')
     return out
