@@ -496,6 +496,48 @@ int deva_merge_paint(const int64_t* ours, const int64_t* news, const int64_t* ne
                      const int32_t* new_order, const int64_t* new_label, const int64_t* out_ids,
                      int n_out, int64_t pixels, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Test-time ensemble (multi-scale / horizontal flip).  The reference spreads the protocol over
+ * evaluation/eval_vos.py --flip (lines 162-164, 176-177: flip image and mask before `step`, flip the
+ * resized probabilities back), --save_scores (lines 188-211: (prob * 255).astype(np.uint8) per frame
+ * and run, plus the tmp-id -> object-id table) and scripts/merge_multi_scale.py:44-66 (float32 sum of
+ * the runs' uint8 volumes, np.argmax over channels, id table).
+ *
+ * A variant is one run's probabilities of the frame: `channels` planes of height x width fp32,
+ * rows `row_stride` and planes `plane_stride` elements apart (an un-padded view of a padded tensor
+ * needs no copy), produced from the mirrored frame when `flip` is set.  Its resize to the output size
+ * uses the arithmetic of deva_index_mask (F.interpolate bilinear, align_corners=False; the source
+ * itself at equal sizes); a flipped variant is resized first and mirrored second, as the reference
+ * does. */
+#define DEVA_ENSEMBLE_MAX_VARIANTS 8
+typedef struct deva_ensemble_variant {
+  const float* src;
+  int64_t plane_stride;
+  int64_t row_stride;
+  int32_t channels, height, width;
+  int32_t flip;
+} deva_ensemble_variant;
+/* the --save_scores product of one run (eval_vos.py:170-177, 188-189):
+ * out[c][y][x] = (uint8) trunc(255 * resized[c][y][flip ? out_width-1-x : x]), uint8
+ * [channels][out_height][out_width].  Probabilities lie in [0, 1]; other values are clamped to the
+ * byte range. */
+int deva_scores_u8(const deva_ensemble_variant* variant, int out_height, int out_width, uint8_t* out,
+                   void* stream);
+/* the merge of n_variants (1..DEVA_ENSEMBLE_MAX_VARIANTS) runs in one pass, without the score volumes
+ * (merge_multi_scale.py:44-66 over eval_vos.py:162-177, 188-189): per pixel and channel the sum over
+ * the variants of the deva_scores_u8 bytes (quantize != 0, the reference protocol; integer sums) or
+ * of the fp32 resized values in variant order (quantize == 0), then the first-maximum argmax over
+ * channels and out = lut ? lut[argmax] (0 beyond n_lut) : argmax, int64 [out_height][out_width].
+ * All variants must have the same number of channels. */
+int deva_ensemble_index_mask(const deva_ensemble_variant* variants, int n_variants, int out_height,
+                             int out_width, int quantize, const int64_t* lut, int n_lut,
+                             int64_t* out, void* stream);
+/* torch.flip(x, dims=[-1]) of eval_vos.py:162-164 on the input side of a flipped variant:
+ * dst[r][x] = src[r][width-1-x] for `rows` rows of `width` elements of elem_bytes = 1, 3, 4 or 8
+ * bytes (3: the pixels of a uint8 H*W*3 frame; 4: fp32 planes; 8: an int64 index mask).  dst must not
+ * overlap src. */
+int deva_flip_w(const void* src, void* dst, int64_t rows, int width, int elem_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

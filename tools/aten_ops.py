@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Which ATen / runtime kernels does the steady-state frame loop still launch, and from which line?
-    python tools/aten_ops.py [480p|8seg]
+    python tools/aten_ops.py [480p|8seg|ensemble]
 torch.profiler over a few frames of the headline loop (bench.py's clip), CPU-side op records with Python stacks: every
 aten:: op that is not a view / empty, with its call site inside the package, counted per frame.  """
 import collections
@@ -24,6 +24,14 @@ if which == '480p':
     cfg = synth.base_config(enable_long_term=False, enable_long_term_count_usage=False)
     frames = bench.make_clip(480, 854, 8 + frames_n, seed=100, device=dev)
     core = bench.start_clip(net, cfg, frames, 5, dev)
+elif which == 'ensemble':  # the test-time ensemble: uint8 480p frames, 5 objects, the native size and 540, each with the flip
+    from deva.inference.ensemble import EnsembleInferenceCore
+    cfg = synth.base_config(enable_long_term=False, enable_long_term_count_usage=False)
+    mean, std = (torch.tensor(v, device=dev).view(3, 1, 1) for v in ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225)))
+    frames = [((f * std + mean).clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous()
+              for f in bench.make_clip(480, 854, 8 + frames_n, seed=100, device=dev)]
+    core = EnsembleInferenceCore(net, cfg, sizes=(-1, 540), flips=(False, True))
+    core.step(frames[0], synth.box_mask(480, 854, 5).to(dev), [1, 2, 3, 4, 5])
 else:
     cfg = synth.base_config()
     frames = bench.make_clip(1080, 1920, 8 + frames_n, seed=7, device=dev)

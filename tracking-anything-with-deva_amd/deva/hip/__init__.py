@@ -40,6 +40,19 @@ class ConvDesc(Structure):
     ]
 
 
+ENSEMBLE_MAX_VARIANTS = 8
+
+
+class EnsembleVariant(Structure):
+    """mirror of `struct deva_ensemble_variant` (include/deva_hip.h)"""
+    _fields_ = [
+        ('src', c_void_p),
+        ('plane_stride', c_int64), ('row_stride', c_int64),
+        ('channels', c_int32), ('height', c_int32), ('width', c_int32),
+        ('flip', c_int32),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol of include/deva_hip.h
 SIGNATURES = {
     'deva_hip_version': (c_int, []),
@@ -115,6 +128,10 @@ SIGNATURES = {
     'deva_index_mask': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'deva_merge_paint': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    'deva_scores_u8': (c_int, [POINTER(EnsembleVariant), c_int, c_int, c_void_p, c_void_p]),
+    'deva_ensemble_index_mask': (c_int, [POINTER(EnsembleVariant), c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                         c_void_p]),
+    'deva_flip_w': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
 }
 
 _LIB = None

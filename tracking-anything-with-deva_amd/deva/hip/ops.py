@@ -11,14 +11,15 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SQUARE_PLUS_ONE, KLAYOUT_CHUNK32, KLAYOUT_Q4, KLAYOUT_TAP_MAJOR,
-               ConvDesc, DevaHipError, check, lib)
+from . import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SQUARE_PLUS_ONE, ENSEMBLE_MAX_VARIANTS, KLAYOUT_CHUNK32, KLAYOUT_Q4,
+               KLAYOUT_TAP_MAJOR, ConvDesc, DevaHipError, EnsembleVariant, check, lib)
 
 __all__ = ['PackedConv', 'pack_conv', 'conv2d', 'split_fallbacks', 'PackedStem', 'pack_stem', 'stem7x7', 'pad2d', 'usage_init', 'gather_s2', 'maxpool3x3s2', 'upsample2x_add', 'upsample2x_add_ds2', 'clip_index', 'upsample2x_add_map', 'upsample2x_add_ds2_map', 'area_downsample',
            'aggregate', 'softmax_channels', 'upsample4x_softmax', 'cbam', 'gru_update',
            'affinity_topk', 'BankPrep', 'affinity_dense', 'dense_read', 'affinity_candidates', 'affinity_merge', 'usage_update', 'readout_sparse', 'bank_append', 'bank_gather_rows',
            'bank_export', 'rank', 'rank_select', 'evict_select', 'similarity_dense', 'softmax_columns',
            'label_histogram', 'merge_paint', 'lut_remap', 'index_mask', 'input_head',
+           'scores_u8', 'ensemble_index_mask', 'flip_w',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_SQUARE_PLUS_ONE']
 
 
@@ -977,4 +978,64 @@ def input_head(image_u8: torch.Tensor, size: Optional[Tuple[int, int]] = None, *
     sd = (ctypes.c_float * 3)(*std)
     check(lib().deva_input_head(_p(image_u8, torch.uint8, 'image'), h, w, m, sd, int(antialias), _p(out), oh, ow,
                                 left, right, top, bottom, _stream()), 'deva_input_head')
+    return out
+
+
+# ------------------------------------------------------------------------------------------ test-time ensemble
+def _variant(prob: torch.Tensor, flip: bool, what: str) -> EnsembleVariant:
+    """descriptor of one run's [C,H,W] fp32 probabilities; rows and planes may be strided (an `unpad`-ed view)"""
+    if not prob.is_cuda or prob.dtype != torch.float32:
+        raise DevaHipError(f'{what}: fp32 HIP tensors expected (got {prob.dtype} on {prob.device})')
+    if prob.dim() != 3 or prob.stride(2) != 1 or prob.stride(1) < prob.shape[2] or \
+            prob.stride(0) < prob.stride(1) * (prob.shape[1] - 1) + prob.shape[2]:
+        raise DevaHipError(f'{what}: [C,H,W] probabilities with unit column stride and non-overlapping rows expected')
+    c, h, w = prob.shape
+    return EnsembleVariant(prob.data_ptr(), prob.stride(0), prob.stride(1), c, h, w, int(bool(flip)))
+
+
+def scores_u8(prob: torch.Tensor, size: Optional[Tuple[int, int]] = None, flip: bool = False) -> torch.Tensor:
+    """the `--save_scores` volume of one run: [C,H,W] probabilities -> uint8 [C,OH,OW] = trunc(255 * p), p the bilinear
+    resize to `size` (align_corners=False; the input itself at equal sizes), mirrored along W afterwards if `flip`"""
+    import ctypes
+    v = _variant(prob, flip, 'scores_u8')
+    oh, ow = prob.shape[-2:] if size is None else (int(size[0]), int(size[1]))
+    out = torch.empty((prob.shape[0], oh, ow), dtype=torch.uint8, device=prob.device)
+    check(lib().deva_scores_u8(ctypes.byref(v), oh, ow, _p(out, torch.uint8), _stream()), 'deva_scores_u8')
+    return out
+
+
+def ensemble_index_mask(probs, size: Tuple[int, int], flips, lut: Optional[torch.Tensor] = None,
+                        quantize: bool = True) -> torch.Tensor:
+    """K runs' [C,H_k,W_k] probabilities (K <= 8) -> int64 [OH,OW] labels: per pixel and channel the sum over the runs
+    of the `scores_u8` bytes (quantize=True, the reference's offline merge) or of the fp32 resized values, first-maximum
+    argmax over C, then lut[argmax] if a table is given.  No score volume is written."""
+    probs, flips = list(probs), list(flips)
+    if len(probs) != len(flips):
+        raise DevaHipError('ensemble_index_mask: one flip flag per variant')
+    if not 1 <= len(probs) <= ENSEMBLE_MAX_VARIANTS:
+        raise DevaHipError(f'ensemble_index_mask: 1 to {ENSEMBLE_MAX_VARIANTS} variants (got {len(probs)})')
+    if any(p.device != probs[0].device for p in probs):
+        raise DevaHipError('ensemble_index_mask: all variants must be on one device')
+    variants = (EnsembleVariant * len(probs))(*[_variant(p, f, 'ensemble_index_mask') for p, f in zip(probs, flips)])
+    oh, ow = int(size[0]), int(size[1])
+    out = torch.empty((oh, ow), dtype=torch.int64, device=probs[0].device)
+    n = 0 if lut is None else lut.numel()
+    check(lib().deva_ensemble_index_mask(variants, len(probs), oh, ow, int(bool(quantize)), _p(lut, torch.int64), n,
+                                         _p(out, torch.int64), _stream()), 'deva_ensemble_index_mask')
+    return out
+
+
+def flip_w(x: torch.Tensor) -> torch.Tensor:
+    """torch.flip(x, dims=[-1]) in one launch for a contiguous tensor with 1-, 4- or 8-byte elements, or
+    torch.flip(x, dims=[1]) for a uint8 [H,W,3] frame (its pixels are 3-byte elements)"""
+    if not x.is_cuda or not x.is_contiguous() or x.dim() < 1 or x.numel() == 0:
+        raise DevaHipError('flip_w: a non-empty contiguous HIP tensor expected')
+    if x.dtype == torch.uint8 and x.dim() == 3 and x.shape[2] == 3:
+        rows, width, elem = x.shape[0], x.shape[1], 3
+    elif x.element_size() in (1, 4, 8):
+        rows, width, elem = x.numel() // x.shape[-1], x.shape[-1], x.element_size()
+    else:
+        raise DevaHipError('flip_w: 1-, 4- or 8-byte elements, or a uint8 [H,W,3] frame expected')
+    out = _alloc(x.shape, x.device) if x.dtype == torch.float32 else torch.empty_like(x)
+    check(lib().deva_flip_w(x.data_ptr(), out.data_ptr(), rows, width, elem, _stream()), 'deva_flip_w')
     return out

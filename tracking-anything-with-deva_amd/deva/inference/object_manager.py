@@ -149,7 +149,10 @@ class ObjectManager:
         return new_mask
 
     def get_tmp_to_obj_mapping(self) -> Dict[int, int]:
-        return {obj.id: tmp_id for obj, tmp_id in self.tmp_id_to_obj.items()}
+        # {object id: tmp id}, the table scripts/merge_multi_scale.py:61-64 reads back.  NB the reference unpacks the
+        # items of tmp_id_to_obj as (obj, tmp_id) (object_manager.py:119-121) and so raises AttributeError on an int
+        # as soon as an object exists; the intended mapping is returned here instead of raising.
+        return {obj.id: tmp_id for tmp_id, obj in self.tmp_id_to_obj.items()}
 
     def realize_dict(self, obj_dict: Dict[int, torch.Tensor]) -> torch.Tensor:
         """{object id: tensor} -> stacked tensor in tmp-id order"""
