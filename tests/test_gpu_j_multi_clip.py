@@ -162,7 +162,6 @@ def test_480p_position_independence(network):
 def test_480p_stage_parity(network):
     """batched key encoder + key projection at B = 4 and the ragged batched decoder against the same stages per clip
     (lock-step stage bound 2e-4 relative: batching changes the kernel choice, not the arithmetic's accuracy)"""
-    from deva.hip import ops
     from deva.utils.tensor_utils import pad_divide_by
     g = network.graph()
     imgs = [pad_divide_by(synth.FrameStream(H480, W480, seed=20 + i).next().to(dev()), 16)[0].unsqueeze(0) for i in range(4)]
@@ -187,15 +186,60 @@ def test_480p_stage_parity(network):
     last16 = torch.rand(no, 1, h, w, generator=gen).to(dev())
     f16 = ms_b[0]
     d8, d4 = g.decoder_skips(ms_b[1], ms_b[2])
-    sens_b, logits_b = g.decode_multi(f16, d8, d4, clip, ops.clip_index(clip, 4, dev()), readout, sensory, last16, True)
+    sens_b, logits_b = g.decode(f16, d8, d4, readout, sensory, last16, True, clip=clip)
     at = 0
     for p, n in enumerate(n_objs):
         ms = per[p][0]
-        s, lg = g.decode(ms, readout[at:at + n].contiguous(), sensory[at:at + n].contiguous(),
-                         last16[at:at + n].contiguous(), True)
+        s, lg = g.decode(ms[0], *g.decoder_skips(ms[1], ms[2]), readout[at:at + n].contiguous(),
+                         sensory[at:at + n].contiguous(), last16[at:at + n].contiguous(), True)
         assert rel_err(logits_b[at:at + n], lg) <= 2e-4, ('logits', p, rel_err(logits_b[at:at + n], lg))
         assert rel_err(sens_b[at:at + n], s) <= 2e-4, ('sensory', p, rel_err(sens_b[at:at + n], s))
         at += n
+
+
+def _one_small_frame(network, no):
+    """one 64 x 96 frame (a 4 x 6 map at 1/16) and random per-object decoder / value-encoder inputs for `no` objects"""
+    H, W = 64, 96
+    img = synth.FrameStream(H, W, seed=40).next().to(dev()).unsqueeze(0)
+    ms, _ = network.encode_image(img)
+    gen = torch.Generator().manual_seed(4)
+    readout = torch.randn(no, network.value_dim, H // 16, W // 16, generator=gen).to(dev())
+    sensory = torch.randn(no, network.value_dim, H // 16, W // 16, generator=gen).to(dev()) * 0.5
+    masks = torch.rand(no, H, W, generator=gen).to(dev())
+    return img, ms, readout, sensory, masks
+
+
+def test_plain_graph_call_equals_a_batch_of_one_clip(network):
+    """`CompiledGraph.decode` / `encode_mask` have one body: called plainly with 3 objects (split convolutions, broadcast
+    up-sampling) and as a batch of one clip (`clip=[0, 0, 0]`: the split whatever the count, mapped up-sampling) they
+    launch the same arithmetic -- logits, sensory and value bit for bit"""
+    from deva.hip import ops
+    g = network.graph()
+    img, ms, readout, sensory, masks = _one_small_frame(network, 3)
+    last16 = ops.area_downsample(masks, 16).unsqueeze(1)
+    d8, d4 = g.decoder_skips(ms[1], ms[2])
+    for update in (True, False):
+        s_a, lg_a = g.decode(ms[0], d8, d4, readout, sensory, last16, update)
+        s_b, lg_b = g.decode(ms[0], d8, d4, readout, sensory, last16, update, clip=[0, 0, 0])
+        assert torch.equal(lg_a, lg_b) and torch.equal(s_a, s_b), update
+    v_a, n_a = g.encode_mask(img, ms[0], sensory, masks.unsqueeze(1), True)
+    v_b, n_b = g.encode_mask(img, ms[0], sensory, masks.unsqueeze(1), True, clip=[0, 0, 0])
+    assert torch.equal(v_a, v_b) and torch.equal(n_a, n_b)
+
+
+def test_plain_graph_call_with_one_object_is_segment(network):
+    """the single-launch rule: one object runs the fusers' first convolutions as ONE two-source launch, in the plain
+    graph call as in `DEVA.segment` / `DEVA.encode_mask` on the same inputs -- bit for bit"""
+    from deva.hip import ops
+    g = network.graph()
+    img, ms, readout, sensory, masks = _one_small_frame(network, 1)
+    s, lg = g.decode(ms[0], *g.decoder_skips(ms[1], ms[2]), readout, sensory, ops.area_downsample(masks, 16).unsqueeze(1), True)
+    sens, logits, prob = network.segment(ms, readout.unsqueeze(0), sensory.unsqueeze(0), masks.unsqueeze(0))
+    want_logits, want_prob = network.soft_aggregate(lg[:, 0])
+    assert torch.equal(sens[0], s) and torch.equal(logits[0], want_logits) and torch.equal(prob[0], want_prob)
+    v, n = g.encode_mask(img, ms[0], sensory, masks.unsqueeze(1), True)
+    value, new_h = network.encode_mask(img, ms, sensory.unsqueeze(0), masks.unsqueeze(0))
+    assert torch.equal(value[0], v) and torch.equal(new_h[0], n)
 
 
 def test_480p_single_clip_bit_identical_to_step(network):

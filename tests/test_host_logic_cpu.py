@@ -577,6 +577,29 @@ def test_memory_manager_keys_its_prepared_banks_on_the_versions(emu):
     assert 0 not in mem._bank_prep and 1 in mem._bank_prep
 
 
+def test_broadcasts_are_the_identity_outside_frame_owner_mode():
+    """the one frame of `DEVAInferenceCore` calls the manager's broadcasts on every path: on a manager that is not in
+    frame-owner mode they hand back the very objects they were given -- no copy, no process group, no traffic counted"""
+    import torch.distributed as dist
+    from deva.inference.memory_manager import MemoryManager
+    mem = MemoryManager(synth.base_config())
+    assert not dist.is_initialized() and mem.is_frame_owner and not mem.frame_owner_mode
+    h, w = 4, 6
+    key, sel = torch.randn(1, 64, h, w), torch.rand(1, 64, h, w)
+    shr, value = torch.rand(1, 1, h, w) + 1, torch.randn(1, 2, 512, h, w)
+    before = mem.comm_bytes
+    qk, qe = mem.broadcast_query(key, sel, h, w, key.device)
+    assert qk is key and qe is sel
+    k, s, v, e = mem.broadcast_memory_frame(key, shr, value, sel, [1, 2], h, w, key.device)
+    assert k is key and s is shr and v is value and e is sel
+    data = b'x'
+    assert mem.broadcast_bytes(data, key.device) is data
+    assert mem.comm_bytes == before and not dist.is_initialized()
+    # a read sharded WITHOUT an owner (every rank steps the clip) is not frame-owner mode either
+    mem._shard_group = object()
+    assert mem.broadcast_query(key, sel, h, w, key.device)[0] is key and mem.broadcast_bytes(data, key.device) is data
+
+
 def test_winograd_weights_follow_the_flags(emu, recipe_state_dict):
     """which convolutions carry Winograd-transformed weights (deva/model/_graph.py:WINO_SCOPES): the 3x3 layers of the value
     encoder, the mask decoder and the key encoder by default; none with --no_winograd, --f16_split or --amp (their kernels take

@@ -199,9 +199,14 @@ class MemoryManager:
                 self.long_mem.shard_values(rank, world)
 
     @property
+    def frame_owner_mode(self) -> bool:
+        """one rank of the shard group owns the encoder / decoder (`shard_queries` / `shard_bank` with `owner=`)"""
+        return self._shard_group is not None and self._shard_owner is not None
+
+    @property
     def is_frame_owner(self) -> bool:
         """True unless another rank owns the encoder / decoder of this clip"""
-        if self._shard_group is None or self._shard_owner is None:
+        if not self.frame_owner_mode:
             return True
         import torch.distributed as dist
         return dist.get_rank(self._shard_group) == self._shard_owner
@@ -419,7 +424,9 @@ class MemoryManager:
         """frame-owner mode, memory frame: the owner's new key (1*CK*h*w), shrinkage (1*1*h*w), selection
         (1*CK*h*w) and value (1*objects*CV*h*w) rows are broadcast as one packed buffer so that every rank
         appends the same tokens to its replica -- the 'RCCL all-gather of memory keys' of BASELINE.json.
-        The other ranks pass None for the tensors and receive them."""
+        The other ranks pass None for the tensors and receive them.  Outside frame-owner mode: the arguments themselves."""
+        if not self.frame_owner_mode:
+            return key, shrinkage, value, selection
         import torch.distributed as dist
         ck, cv = self.key_dim, self.sensory_dim
         nobj = len(objects)
@@ -434,7 +441,10 @@ class MemoryManager:
                 packed[2 * ck + 1:].view(1, nobj, cv, h, w), packed[ck + 1:2 * ck + 1].view(1, ck, h, w))
 
     def broadcast_query(self, key, selection, h: int, w: int, device):
-        """frame-owner mode, every frame: the owner's query key / selection (1*CK*h*w each) -> all ranks"""
+        """frame-owner mode, every frame: the owner's query key / selection (1*CK*h*w each) -> all ranks; outside
+        frame-owner mode: the arguments themselves"""
+        if not self.frame_owner_mode:
+            return key, selection
         import torch.distributed as dist
         ck = self.key_dim
         packed = (torch.cat([key[0].reshape(ck, h * w), selection[0].reshape(ck, h * w)], 0) if self.is_frame_owner
@@ -445,7 +455,10 @@ class MemoryManager:
 
     def broadcast_bytes(self, data: Optional[bytes], device) -> bytes:
         """frame-owner mode: host-side bytes of the owner (the object table after a detection frame, the result of a
-        vote) -> every rank, as an int64 length and then the payload (uint8 on `device`).  The other ranks pass None."""
+        vote) -> every rank, as an int64 length and then the payload (uint8 on `device`).  The other ranks pass None.
+        Outside frame-owner mode: `data` itself."""
+        if not self.frame_owner_mode:
+            return data
         import torch.distributed as dist
         src = self._owner_global_rank()
         own = self.is_frame_owner

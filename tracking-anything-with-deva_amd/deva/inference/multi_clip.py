@@ -19,14 +19,13 @@ A group of one clip is routed to `core.step` itself (bit-identical).  Batching c
 convolutions (Winograd threshold, split-K, tile policy), so a batched clip matches its sequential run to round-off, not bit
 for bit.
 """
-import warnings
 from typing import Dict, List, Optional
 
 import torch
 
 from deva.hip import ops
 from deva.inference.inference_core import DEVAInferenceCore
-from deva.utils.tensor_utils import pad_divide_by, unpad
+from deva.utils.tensor_utils import unpad
 
 
 def _batch_of(items: List[torch.Tensor]) -> torch.Tensor:
@@ -96,24 +95,18 @@ def step_clips(cores: List[DEVAInferenceCore], images: List[torch.Tensor],
 
 
 class _Clip:
-    """one clip's frame inside a batched call: the locals of `DEVAInferenceCore.step`"""
+    """one clip's frame inside a batched call: what `_step_group` carries from one batched pass to the next"""
 
-    def __init__(self, core, image, mask, objects, hard_mask, end):
+    def __init__(self, core, image, mask, objects, end):
         self.core, self.mask, self.objects, self.end = core, mask, objects, end
-        self.annotated = mask is not None
-        if self.annotated and objects is None:
-            assert not hard_mask
-            self.objects = list(range(1, mask.shape[0] + 1))
-        core.curr_ti += 1
-        self.frame_ti = core.curr_ti
-        padded, core.pad = pad_divide_by(image, 16)
-        self.batch = padded.unsqueeze(0)
+        self.frame_ti, self.batch = core._advance(image)
         self.prob = None
 
 
 def _step_group(cores, images, masks, objects, hard_mask, end) -> List[torch.Tensor]:
-    g = cores[0].network.graph()
-    clips = [_Clip(*a, hard_mask, e) for a, e in zip(zip(cores, images, masks, objects), end)]
+    net = cores[0].network
+    g = net.graph()
+    clips = [_Clip(*a) for a in zip(cores, images, masks, objects, end)]
 
     # 1. key encoder + key projection over the clips whose store lacks the frame
     todo = [c for c in clips if c.frame_ti not in c.core.image_feature_store]
@@ -128,53 +121,37 @@ def _step_group(cores, images, masks, objects, hard_mask, end) -> List[torch.Ten
         store = c.core.image_feature_store
         c.ms = store.get_ms_features(c.frame_ti, c.batch)
         c.key, c.shrinkage, c.selection = store.get_key(c.frame_ti, c.batch)
-        om = c.core.object_manager
-        due = c.core.curr_ti - c.core.last_mem_ti >= c.core.mem_every
-        c.commit = (c.annotated or due) and not c.end
-        c.propagate = (not c.annotated) or (om.num_obj > 0 and not om.has_all(c.objects))
+        c.objects, c.commit, c.propagate = c.core._plan(c.mask, c.objects, hard_mask, c.end)
 
     # 2. + 3. memory read per clip, one decoder pass over the objects of all propagating clips
     decoding = []
     for c in clips:
         if not c.propagate:
             continue
-        if not c.core.memory.engaged or not c.core.object_manager.all_obj_ids:
+        mem, om = c.core.memory, c.core.object_manager
+        if not mem.engaged or not om.all_obj_ids:
             c.prob = c.core._segment(c.key, c.selection, c.ms, update_sensory=not c.end)  # (warns like `step`)
             continue
-        mem, om = c.core.memory, c.core.object_manager
         c.ids = om.all_obj_ids
         c.readout = om.realize_dict(mem.match_memory(c.key, c.selection))
         c.sensory = mem.get_sensory(c.ids)[0]
         decoding.append(c)
     if decoding:
-        _decode(g, decoding)
+        _decode(net, decoding)
 
-    # 4. annotations per clip, as `step`
+    # 4. annotations per clip
     for c in clips:
-        core, om = c.core, c.core.object_manager
-        if c.annotated:
-            new_tmp_ids, _ = om.add_new_objects(c.objects)
-            mask, _ = pad_divide_by(c.mask, 16)
-            if c.propagate:
-                mask = core._blend_annotation(c.prob, mask, c.objects, new_tmp_ids, hard_mask)
-            elif hard_mask:
-                mask = torch.stack([mask == o for o in c.objects], dim=0)
-            c.prob = ops.softmax_channels(core.network.aggregate(mask, dim=0))
-        core.last_mask = c.prob[1:].unsqueeze(0)
+        c.prob = c.core._annotate(c.prob, c.mask, c.objects, hard_mask, c.propagate)
 
     # 5. value encoder over the objects of the committing clips
     committing = []
     for c in clips:
-        if not c.commit:
-            continue
-        if c.core.last_mask.shape[1] == 0:
-            warnings.warn('Empty object mask!', RuntimeWarning)
-            continue
-        c.ids = c.core.object_manager.all_obj_ids
-        c.core.memory.initialize_sensory_if_needed(c.key, c.ids)
-        committing.append(c)
+        if c.commit:
+            c.ids = c.core._memory_frame_ids(c.core.last_mask, c.key)
+            if c.ids is not None:
+                committing.append(c)
     if committing:
-        _encode_values(g, committing)
+        _encode_values(net, committing)
 
     for c in clips:
         c.core.image_feature_store.delete(c.frame_ti)
@@ -196,51 +173,25 @@ def _object_rows(clips):
     return clip, spans
 
 
-def _decode(g, clips) -> None:
+def _decode(net, clips) -> None:
     """`DEVA.segment` of every clip, the network passes batched over all their objects"""
     clip, spans = _object_rows(clips)
-    f16 = _batch_of([c.ms[0] for c in clips])
-    d8, d4 = g.decoder_skips(_batch_of([c.ms[1] for c in clips]), _batch_of([c.ms[2] for c in clips]))
-    readout = _cat([c.readout for c in clips])
-    sensory = _cat([c.sensory for c in clips])
-    last = _cat([c.core.last_mask[0] for c in clips])
-    last16 = ops.area_downsample(last, last.shape[-1] // readout.shape[-1]).unsqueeze(1)
-    update = any(not c.end for c in clips)
-    no = len(clip)
-    step = _chunk([c.core for c in clips]) or no
-    logits, sens = [], []
-    for i in range(0, no, step):
-        part = clip[i:i + step]
-        s, lg = g.decode_multi(f16, d8, d4, part, ops.clip_index(part, len(clips), readout.device), readout[i:i + step],
-                               sensory[i:i + step], last16[i:i + step], update)
-        logits.append(lg)
-        sens.append(s)
-    obj_logits = (logits[0] if len(logits) == 1 else torch.cat(logits, 0))[:, 0]
-    new_sens = sens[0] if len(sens) == 1 else torch.cat(sens, 0)
+    ms = tuple(_batch_of([c.ms[k] for c in clips]) for k in range(3))
+    new_sens, obj_logits = net.decode_objects(ms, _cat([c.readout for c in clips]), _cat([c.sensory for c in clips]),
+                                              _cat([c.core.last_mask[0] for c in clips]), any(not c.end for c in clips),
+                                              _chunk([c.core for c in clips]), clip)
     for c, (a, b) in zip(clips, spans):
-        _, c.prob = ops.upsample4x_softmax(ops.aggregate(obj_logits[a:b], apply_sigmoid=True))
+        _, c.prob = net.soft_aggregate(obj_logits[a:b])
         if not c.end:
             c.core.memory.update_sensory(new_sens[a:b].unsqueeze(0), c.ids)
 
 
-def _encode_values(g, clips) -> None:
+def _encode_values(net, clips) -> None:
     """`DEVAInferenceCore._add_memory` of every clip, the value encoder batched over all their objects"""
     clip, spans = _object_rows(clips)
-    images = _cat([c.batch for c in clips])
-    f16 = _batch_of([c.ms[0] for c in clips])
     sensory = _cat([c.core.memory.get_sensory(c.ids)[0] for c in clips])
-    masks = _cat([c.core.last_mask[0] for c in clips]).unsqueeze(1)
-    no = len(clip)
-    step = _chunk([c.core for c in clips]) or no
-    values, sens = [], []
-    for i in range(0, no, step):
-        v, s = g.encode_mask_multi(images, f16, clip[i:i + step], sensory[i:i + step], masks[i:i + step], True)
-        values.append(v)
-        sens.append(s)
-    value = values[0] if len(values) == 1 else torch.cat(values, 0)
-    new_sens = sens[0] if len(sens) == 1 else torch.cat(sens, 0)
+    value, new_sens = net.encode_objects(_cat([c.batch for c in clips]), _batch_of([c.ms[0] for c in clips]), sensory,
+                                         _cat([c.core.last_mask[0] for c in clips]), True,
+                                         _chunk([c.core for c in clips]), clip)
     for c, (a, b) in zip(clips, spans):
-        mem = c.core.memory
-        mem.add_memory(c.key, c.shrinkage, value[a:b].unsqueeze(0), c.ids, selection=c.selection)
-        c.core.last_mem_ti = c.core.curr_ti
-        mem.update_sensory(new_sens[a:b].unsqueeze(0), c.ids)
+        c.core._commit_value(c.key, c.shrinkage, c.selection, value[a:b].unsqueeze(0), new_sens[a:b].unsqueeze(0), c.ids)

@@ -228,15 +228,35 @@ class CompiledGraph:
             pc = self.s2[base] = ops.pack_conv(w1, b, None, self.device, split=True)
         return pc
 
-    def _conv_shared_x(self, base: str, x, g, **kw):
-        """conv over the virtual cat(x broadcast, g): one launch for a single object, otherwise the image
-        part once + the per-object part with it as the fused residual"""
+    # `clip` below: several clips in one pass (deva/inference/multi_clip.py).  x is then [B,C,h,w], one image feature per
+    # clip (a batch-strided view of the batched key encoder's output is fine, the convolutions take a batch stride), and
+    # `clip` the host list of each object's clip (index into x).  Without it x is [1,C,h,w] and broadcasts.
+    @staticmethod
+    def _per_object(t, clip):
+        """t [B,...] per clip -> what object i reads as t[clip[i]]: t itself when it broadcasts (B = 1), a slice when the
+        objects are consecutive clips, otherwise a row gather"""
+        if t.shape[0] == 1:
+            return t
+        lo = clip[0]
+        if clip == list(range(lo, lo + len(clip))):
+            return t[lo:lo + len(clip)]
+        out = ops._alloc((len(clip), *t.shape[1:]), t.device)
+        ops.bank_gather_rows(t.reshape(t.shape[0], -1), ops.clip_index(clip, t.shape[0], t.device),
+                             out.view(len(clip), -1), len(clip))
+        return out
+
+    def _conv_shared_x(self, base: str, x, g, clip=None, **kw):
+        """conv over the virtual cat(x broadcast, g) or, with `clip`, cat(x[clip[i]], g[i]): the image part once (per clip) +
+        the per-object part with it as the fused residual; without `clip`, a single object (or a layer without split
+        weights) takes one two-source launch"""
         amp, sp = self._amp_of(base), self._split_of(base)
-        if g.shape[0] < 2 or x.shape[0] != 1 or base not in self.split:
+        if clip is None and (g.shape[0] < 2 or x.shape[0] != 1 or base not in self.split):
             return ops.conv2d(self.convs[base], x, g, amp=amp, split=sp, **kw)
         wx, wg = self.split[base]
         act = kw.pop('act', 0)  # the activation belongs to the sum of the two parts
         shared = ops.conv2d(wx, x, amp=amp, split=sp, **kw)
+        if clip is not None:
+            shared = self._per_object(shared, clip)
         return ops.conv2d(wg, g, residual=shared, amp=amp, split=sp, act=act, **kw)
 
     def _bn_after(self, conv: str):
@@ -272,21 +292,21 @@ class CompiledGraph:
             x = block_fn(f'{pre}.{i}', x, stride if i == 0 else 1)
         return x
 
-    def _res_block(self, pre: str, g0, g1=None):
+    def _res_block(self, pre: str, g0, g1=None, clip=None):
         """relu -> 3x3 -> relu -> 3x3, plus (1x1-projected) input; input = virtual cat(g0, g1).  The inner ReLU is
         conv1's output stage (its result feeds conv2 only), so conv2 reads its input as it is."""
         c = self.convs
         if g1 is not None:
-            t = self._conv_shared_x(pre + '.conv1', g0, g1, pad=1, relu_in=True, act=ACT_RELU)
-            skip = self._conv_shared_x(pre + '.downsample', g0, g1)
+            t = self._conv_shared_x(pre + '.conv1', g0, g1, clip, pad=1, relu_in=True, act=ACT_RELU)
+            skip = self._conv_shared_x(pre + '.downsample', g0, g1, clip)
         else:
             t = self._conv(pre + '.conv1', g0, pad=1, relu_in=True, act=ACT_RELU)
             skip = self._conv(pre + '.downsample', g0) if (pre + '.downsample') in c else g0
         return self._conv(pre + '.conv2', t, pad=1, residual=skip)
 
-    def _fusion(self, pre: str, x, g):
-        """x [1,Cx,h,w] image feature (broadcast over objects), g [no,Cg,h,w]"""
-        g = self._res_block(pre + '.block1', x, g)
+    def _fusion(self, pre: str, x, g, clip=None):
+        """x [1,Cx,h,w] image feature (broadcast over objects; [B,Cx,h,w] with `clip`), g [no,Cg,h,w]"""
+        g = self._res_block(pre + '.block1', x, g, clip)
         a = pre + '.attention.ChannelGate.mlp.'
         g = ops.cbam(g, self.vecs[a + '1.weight'], self.vecs[a + '1.bias'], self.vecs[a + '3.weight'],
                      self.vecs[a + '3.bias'], self.convs[pre + '.attention.SpatialGate.spatial.conv'])
@@ -316,47 +336,54 @@ class CompiledGraph:
         selection = self._conv('key_proj.e_proj', feat, pad=1, act=ACT_SIGMOID) if need_e else None
         return self._conv('key_proj.key_proj', feat, pad=1), shrinkage, selection
 
-    def encode_mask(self, image, f16, sensory, masks, deep_update: bool):
-        """image [1,3,H,W]; masks [no,1,H,W]; sensory [no,C,h,w] -> value [no,C,h,w], sensory'"""
-        c = self.convs
+    def encode_mask(self, image, f16, sensory, masks, deep_update: bool, clip=None):
+        """image [1,3,H,W] and f16 [1,...] (with `clip`: [B,...] per clip, object i belongs to clip[i]); masks [no,1,H,W];
+        sensory [no,C,h,w] -> value [no,C,h,w], sensory'"""
         me = 'mask_encoder'
         if (me + '.conv1') in self.stems:
-            g = ops.stem7x7(self.stems[me + '.conv1'], image, masks)
+            g = ops.stem7x7(self.stems[me + '.conv1'], image if clip is None else self._per_object(image, clip), masks)
         else:
-            g = self._conv_shared_x(me + '.conv1', image, masks, stride=2, pad=3)
+            g = self._conv_shared_x(me + '.conv1', image, masks, clip, stride=2, pad=3)
         g = ops.maxpool3x3s2(g, relu_after=True)
         g = self._stage(me + '.layer1', g, 2, 1, self._basic)
         g = self._stage(me + '.layer2', g, 2, 2, self._basic)
         g = self._stage(me + '.layer3', g, 2, 2, self._basic)
-        value = self._fusion(me + '.fuser', f16, g)
+        value = self._fusion(me + '.fuser', f16, g, clip)
         if deep_update:
             sensory = self._gru(me + '.sensory_update.transform', value, sensory)
         return value, sensory
 
-    def decode_masks(self, ms_features, readout, sensory, last_mask16, want_p8_ds: bool = False):
-        """readout/sensory [no,C,h,w]; last_mask16 [no,1,h,w] -> decoder pyramid p16, p8, p4, the object logits
-        [no,1,4h,4w] (everything `segment` returns except the new sensory state) and, with want_p8_ds, p8 at 1/16 for
-        `sensory_update` (None otherwise)"""
-        c = self.convs
+    def decoder_skips(self, f8, f4):
+        """the image-only inputs of the decoder's up-sampling blocks: f8 / f4 [B,...] -> d8, d4"""
+        md = 'mask_decoder.decoder_feat_proc.transforms.'
+        return self._conv(md + '0', f8), self._conv(md + '1', f4)
+
+    def decode_masks(self, f16, d8, d4, readout, sensory, last_mask16, want_p8_ds: bool = False, clip=None):
+        """f16 and the skips d8 / d4 [1,...] (with `clip`: [B,...] per clip, object i belongs to clip[i]); readout / sensory
+        [no,C,h,w]; last_mask16 [no,1,h,w] -> decoder pyramid p16, p8, p4, the object logits [no,1,4h,4w] (everything
+        `segment` returns except the new sensory state) and, with want_p8_ds, p8 at 1/16 for `sensory_update` (None
+        otherwise)"""
         md = 'mask_decoder'
-        f16, f8, f4 = ms_features
-        d8 = self._conv(md + '.decoder_feat_proc.transforms.0', f8)
-        d4 = self._conv(md + '.decoder_feat_proc.transforms.1', f4)
+        if clip is None:
+            up2, up2_ds2 = ops.upsample2x_add, ops.upsample2x_add_ds2
+        else:  # the skip of object i is d[clip[i]]: the mapped up-sampling kernels
+            clip_dev = ops.clip_index(clip, f16.shape[0], readout.device)
+            up2 = lambda p, d: ops.upsample2x_add_map(p, d, clip_dev)
+            up2_ds2 = lambda p, d: ops.upsample2x_add_ds2_map(p, d, clip_dev)
         p16 = self._conv(md + '.sensory_compress', sensory, last_mask16, residual=readout)
-        p16 = self._fusion(md + '.fuser', f16, p16)
-        p8 = self._res_block(md + '.up_16_8.out_conv', ops.upsample2x_add(p16, d8))
+        p16 = self._fusion(md + '.fuser', f16, p16, clip)
+        p8 = self._res_block(md + '.up_16_8.out_conv', up2(p16, d8))
         if want_p8_ds and p8.shape[-2] % 2 == 0 and p8.shape[-1] % 2 == 0:
             # the sensory update takes p8 at 1/16 (modules.py:121-151): written by the pass that up-samples p8 anyway
-            up, p8_ds = ops.upsample2x_add_ds2(p8, d4)
+            up, p8_ds = up2_ds2(p8, d4)
         else:
-            up, p8_ds = ops.upsample2x_add(p8, d4), None
+            up, p8_ds = up2(p8, d4), None
         p4 = self._res_block(md + '.up_8_4.out_conv', up)
         logits = self._conv(md + '.pred', p4, pad=1, relu_in=True)
         return p16, p8, p4, logits, p8_ds
 
     def sensory_update(self, p16, p8, p4, logits, sensory, p8_ds=None):
         """the decoder's GRU update of the sensory memory (modules.py:121-151): needed by the NEXT frame only"""
-        c = self.convs
         su = 'mask_decoder.sensory_update'
         g = self._conv(su + '.g16_conv', p16)
         if p8_ds is None:  # (decode_masks(want_p8_ds=True) makes it in its x2 up-sampling pass)
@@ -365,85 +392,10 @@ class CompiledGraph:
         g = self._conv(su + '.g4_conv', ops.area_downsample(p4, 4), ops.area_downsample(logits, 4), residual=g)
         return self._gru(su + '.transform', g, sensory)
 
-    def decode(self, ms_features, readout, sensory, last_mask16, update_sensory: bool):
-        """readout/sensory [no,C,h,w]; last_mask16 [no,1,h,w] -> sensory', object logits [no,1,4h,4w]"""
-        p16, p8, p4, logits, p8_ds = self.decode_masks(ms_features, readout, sensory, last_mask16, want_p8_ds=update_sensory)
+    def decode(self, f16, d8, d4, readout, sensory, last_mask16, update_sensory: bool, clip=None):
+        """`decode_masks` + `sensory_update` -> sensory' (the input sensory without update_sensory), object logits
+        [no,1,4h,4w]"""
+        p16, p8, p4, logits, p8_ds = self.decode_masks(f16, d8, d4, readout, sensory, last_mask16, update_sensory, clip)
         if update_sensory:
             sensory = self.sensory_update(p16, p8, p4, logits, sensory, p8_ds)
         return sensory, logits
-
-    # ---------------------------------------------------------------- several clips in one pass (deva/inference/multi_clip.py)
-    # x below is [B,C,h,w]: one image feature per clip (a batch-strided view of the batched key encoder's output is fine, the
-    # convolutions take a batch stride); `clip` is the host list of each object's clip (index into x), and `clip_dev` the
-    # same as an int32 device tensor (ops.clip_index) for the mapped up-sampling kernels.
-    @staticmethod
-    def _per_object(t, clip):
-        """t [B,...] per clip -> what object i reads as t[clip[i]]: t itself when it broadcasts (B = 1), a slice when the
-        objects are consecutive clips, otherwise a row gather"""
-        if t.shape[0] == 1:
-            return t
-        lo = clip[0]
-        if clip == list(range(lo, lo + len(clip))):
-            return t[lo:lo + len(clip)]
-        out = ops._alloc((len(clip), *t.shape[1:]), t.device)
-        ops.bank_gather_rows(t.reshape(t.shape[0], -1), ops.clip_index(clip, t.shape[0], t.device),
-                             out.view(len(clip), -1), len(clip))
-        return out
-
-    def _conv_shared_x_multi(self, base: str, x, g, clip, **kw):
-        """conv over the virtual cat(x[clip[i]], g[i]): the image part once per clip (batch B), entering object i's
-        convolution as its fused residual (the split of `_conv_shared_x`, whatever the number of objects)"""
-        amp, sp = self._amp_of(base), self._split_of(base)
-        wx, wg = self.split[base]
-        act = kw.pop('act', 0)
-        shared = ops.conv2d(wx, x, amp=amp, split=sp, **kw)
-        return ops.conv2d(wg, g, residual=self._per_object(shared, clip), amp=amp, split=sp, act=act, **kw)
-
-    def _fusion_multi(self, pre: str, x, g, clip):
-        b1 = pre + '.block1'
-        t = self._conv_shared_x_multi(b1 + '.conv1', x, g, clip, pad=1, relu_in=True, act=ACT_RELU)
-        skip = self._conv_shared_x_multi(b1 + '.downsample', x, g, clip)
-        g = self._conv(b1 + '.conv2', t, pad=1, residual=skip)
-        a = pre + '.attention.ChannelGate.mlp.'
-        g = ops.cbam(g, self.vecs[a + '1.weight'], self.vecs[a + '1.bias'], self.vecs[a + '3.weight'],
-                     self.vecs[a + '3.bias'], self.convs[pre + '.attention.SpatialGate.spatial.conv'])
-        return self._res_block(pre + '.block2', g)
-
-    def decoder_skips(self, f8, f4):
-        """the image-only inputs of the decoder's up-sampling blocks, once per clip: f8 / f4 [B,...] -> d8, d4"""
-        md = 'mask_decoder.decoder_feat_proc.transforms.'
-        return self._conv(md + '0', f8), self._conv(md + '1', f4)
-
-    def decode_multi(self, f16, d8, d4, clip, clip_dev, readout, sensory, last_mask16, update_sensory: bool):
-        """`decode` over the objects of several clips: f16 / d8 / d4 [B,...] per clip, readout / sensory / last_mask16 per
-        object (object i belongs to clip[i]) -> sensory' (or the input sensory), object logits [no,1,4h,4w]"""
-        md = 'mask_decoder'
-        p16 = self._conv(md + '.sensory_compress', sensory, last_mask16, residual=readout)
-        p16 = self._fusion_multi(md + '.fuser', f16, p16, clip)
-        p8 = self._res_block(md + '.up_16_8.out_conv', ops.upsample2x_add_map(p16, d8, clip_dev))
-        if update_sensory and p8.shape[-2] % 2 == 0 and p8.shape[-1] % 2 == 0:
-            up, p8_ds = ops.upsample2x_add_ds2_map(p8, d4, clip_dev)
-        else:
-            up, p8_ds = ops.upsample2x_add_map(p8, d4, clip_dev), None
-        p4 = self._res_block(md + '.up_8_4.out_conv', up)
-        logits = self._conv(md + '.pred', p4, pad=1, relu_in=True)
-        if update_sensory:
-            sensory = self.sensory_update(p16, p8, p4, logits, sensory, p8_ds)
-        return sensory, logits
-
-    def encode_mask_multi(self, images, f16, clip, sensory, masks, deep_update: bool):
-        """`encode_mask` over the objects of several clips: images [B,3,H,W] and f16 [B,...] per clip; sensory / masks per
-        object (object i belongs to clip[i]) -> value [no,C,h,w], sensory'"""
-        me = 'mask_encoder'
-        if (me + '.conv1') in self.stems:
-            g = ops.stem7x7(self.stems[me + '.conv1'], self._per_object(images, clip), masks)
-        else:
-            g = self._conv_shared_x_multi(me + '.conv1', images, masks, clip, stride=2, pad=3)
-        g = ops.maxpool3x3s2(g, relu_after=True)
-        g = self._stage(me + '.layer1', g, 2, 1, self._basic)
-        g = self._stage(me + '.layer2', g, 2, 2, self._basic)
-        g = self._stage(me + '.layer3', g, 2, 2, self._basic)
-        value = self._fusion_multi(me + '.fuser', f16, g, clip)
-        if deep_update:
-            sensory = self._gru(me + '.sensory_update.transform', value, sensory)
-        return value, sensory

@@ -87,20 +87,21 @@ class DEVA(nn.Module):
         """network.py:46-60.  image [1,3,H,W]; h (sensory) [1,no,C,h,w]; masks [1,no,H,W]
         -> value [1,no,C,h,w], new sensory [1,no,C,h,w]"""
         assert image.shape[0] == 1 and masks.shape[0] == 1, 'batch size 1 (objects are the batch axis)'
+        value, new_h = self.encode_objects(_f32c(image), ms_features[0], _f32c(h)[0], _f32c(masks)[0], is_deep_update,
+                                           chunk_size)
+        return value.unsqueeze(0), new_h.unsqueeze(0)
+
+    def encode_objects(self, image, f16, sensory, masks, is_deep_update: bool, chunk_size, clip=None):
+        """the value encoder over all objects, `chunk_size` at a time: image [1,3,H,W] and f16 [1,...] -- or, with `clip`
+        (the clip of every object), [B,...] per clip; sensory [no,C,h,w]; masks [no,H,W] -> value [no,C,h,w], sensory'"""
         g = self.graph()
-        image, f16 = _f32c(image), ms_features[0]
-        sens_all = _f32c(h)[0]
-        masks_all = _f32c(masks)[0].unsqueeze(1)
-        no = masks_all.shape[0]
-        step = no if (chunk_size < 1 or chunk_size >= no) else chunk_size
+        masks = masks.unsqueeze(1)
         values, sens = [], []
-        for i in range(0, no, step):
-            v, s = g.encode_mask(image, f16, sens_all[i:i + step], masks_all[i:i + step], is_deep_update)
+        for i, j in _chunks(masks.shape[0], chunk_size):
+            v, s = g.encode_mask(image, f16, sensory[i:j], masks[i:j], is_deep_update, None if clip is None else clip[i:j])
             values.append(v)
             sens.append(s)
-        value = values[0] if len(values) == 1 else torch.cat(values, 0)
-        new_h = sens[0] if len(sens) == 1 else torch.cat(sens, 0)
-        return value.unsqueeze(0), new_h.unsqueeze(0)
+        return _cat0(values), _cat0(sens)
 
     def read_memory(self, query_key: torch.Tensor, query_selection: torch.Tensor, memory_key: torch.Tensor,
                     memory_shrinkage: torch.Tensor, memory_value: torch.Tensor) -> torch.Tensor:
@@ -150,24 +151,31 @@ class DEVA(nn.Module):
             raise NotImplementedError('training-only options of DEVA.segment are not part of the '
                                       'inference path (need_aux / selector / independent_objects)')
         assert memory_readout.shape[0] == 1, 'batch size 1 (objects are the batch axis)'
+        new_sens, obj_logits = self.decode_objects(tuple(multi_scale_features), _f32c(memory_readout)[0], _f32c(sensory)[0],
+                                                   _f32c(last_mask)[0], update_sensory, chunk_size)
+        logits_up, prob = self.soft_aggregate(obj_logits)
+        return new_sens.unsqueeze(0), logits_up.unsqueeze(0), prob.unsqueeze(0)
+
+    def decode_objects(self, ms, readout, sensory, last_mask, update_sensory: bool, chunk_size, clip=None):
+        """the mask decoder over all objects, `chunk_size` at a time: ms = (f16, f8, f4), [1,...] each -- or, with `clip`
+        (the clip of every object), [B,...] per clip; readout / sensory [no,C,h,w]; last_mask [no,H,W] -> sensory'
+        [no,C,h,w], object logits [no,H/4,W/4]"""
         g = self.graph()
-        ms = tuple(multi_scale_features)
-        readout_all, sens_all = _f32c(memory_readout)[0], _f32c(sensory)[0]
-        no = readout_all.shape[0]
-        last16 = ops.area_downsample(_f32c(last_mask)[0], last_mask.shape[-1] // readout_all.shape[-1])
-        last16 = last16.unsqueeze(1)
-        step = no if (chunk_size < 1 or chunk_size >= no) else chunk_size
+        last16 = ops.area_downsample(last_mask, last_mask.shape[-1] // readout.shape[-1]).unsqueeze(1)
+        d8, d4 = g.decoder_skips(ms[1], ms[2])
         logits, sens = [], []
-        for i in range(0, no, step):
-            s, lg = g.decode(ms, readout_all[i:i + step], sens_all[i:i + step], last16[i:i + step],
-                             update_sensory)
+        for i, j in _chunks(readout.shape[0], chunk_size):
+            s, lg = g.decode(ms[0], d8, d4, readout[i:j], sensory[i:j], last16[i:j], update_sensory,
+                             None if clip is None else clip[i:j])
             logits.append(lg)
             sens.append(s)
-        obj_logits = (logits[0] if len(logits) == 1 else torch.cat(logits, 0))[:, 0]
-        new_sens = sens[0] if len(sens) == 1 else torch.cat(sens, 0)
-        agg = ops.aggregate(obj_logits, apply_sigmoid=True)
-        logits_up, prob = ops.upsample4x_softmax(agg)
-        return new_sens.unsqueeze(0), logits_up.unsqueeze(0), prob.unsqueeze(0)
+        return _cat0(sens), _cat0(logits)[:, 0]
+
+    @staticmethod
+    def soft_aggregate(obj_logits: torch.Tensor):
+        """object logits [no,h,w] -> (logits, prob) [no+1,4h,4w]: soft aggregation of the sigmoids (network.py:33-40), x4
+        bilinear up-sampling and the channel soft-max"""
+        return ops.upsample4x_softmax(ops.aggregate(obj_logits, apply_sigmoid=True))
 
     def forward(self, mode: str, *args, **kwargs):
         # network.py:175-187
@@ -188,3 +196,13 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32:
         t = t.float()
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _chunks(no: int, chunk_size):
+    """(first, end) object rows of every network pass: all objects in one unless 1 <= chunk_size < no"""
+    step = no if (chunk_size is None or chunk_size < 1 or chunk_size >= no) else chunk_size
+    return [(i, i + step) for i in range(0, no, step)]
+
+
+def _cat0(parts):
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
