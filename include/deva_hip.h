@@ -316,14 +316,12 @@ int deva_affinity_select(const uint64_t* part_keys, int hw, int k, int splits, i
                          uint64_t* out_keys, uint32_t* out_counts, void* stream);
 int deva_affinity_merge(const uint64_t* keys, const uint32_t* counts, int hw, int k, int lists, int32_t* idx,
                         float* weight, uint64_t* usage_fix, void* stream);
-/* Tuning / test hook: force one of the kernel shapes of deva_affinity_topk (1, 6: per-wave candidate lists, one / two
- * workgroups per CU with early key prefetch; 2: two per CU, late prefetch; 3: key tiles shared through LDS; 4, 5:
- * workgroup-shared lists, two / one 4-wave workgroup per CU; 7: ping-pong phases; 8: workgroup-shared lists, one 8-wave
- * workgroup per CU); 0 = automatic choice by frame and bank size (the default; the environment
- * variable DEVA_AFFINITY_SHAPE sets the initial value).  All shapes give bit-identical results.  The product library
- * carries shapes 2, 4 and 8 (the ones the automatic choice uses); 1, 3, 5, 6, 7 are A/B variants of `make PROBES=1`
- * builds and are refused otherwise.  Call between
- * deva_affinity_default_splits / deva_affinity_workspace / deva_affinity_topk sequences, not inside one. */
+/* Tuning / test hook: force one of the kernel shapes of deva_affinity_topk (2: per-wave candidate lists, two workgroups
+ * per CU; 4: workgroup-shared lists, two 4-wave workgroups per CU; 8: workgroup-shared lists, one 8-wave workgroup per
+ * CU); 0 = automatic choice by frame and bank size (the default; the environment variable DEVA_AFFINITY_SHAPE sets the
+ * initial value).  All shapes give bit-identical results.  Every other number is refused, in every build: 1, 3, 5, 6, 7
+ * were A/B variants that round 2 measured as slower (profiles/r02e_affinity_shapes.txt) and no longer exist.  Call
+ * between deva_affinity_default_splits / deva_affinity_workspace / deva_affinity_topk sequences, not inside one. */
 int deva_affinity_force_shape(int shape);
 /* workspace query: number of uint64 elements part_keys must hold */
 int64_t deva_affinity_workspace(int hw, int k, int splits);
@@ -341,7 +339,7 @@ int deva_affinity_dense(const float* key_long, const float* shr_long, int n_long
                         const float* shr_work, int n_work, const float* qk, const float* qe, int hw, int k,
                         int32_t* idx, float* weight, uint64_t* usage_fix, void* stream);
 /* The whole read in one call, with the fp16 pre-filter where it pays (banks of >= 4 096 tokens AND >= 8 000 000
- * (token, query) scores: PF_MIN_TOKENS / PF_MIN_SCORES of csrc/affinity.hip; deva_affinity_prefilter_enabled tells):
+ * (token, query) scores: PF_MIN_TOKENS / PF_MIN_SCORES of csrc/affinity_prefilter.hip; deva_affinity_prefilter_enabled tells):
  *   every (token, query) score is first bounded from both sides with v_mfma_f32_32x32x16_f16 on fp16 copies of the
  *   operands (1/16 of the fp32 matrix time) under a rigorous error bound, a filter threshold is derived from group
  *   maxima of the lower bounds, and only the tokens whose upper bound reaches it (~k + 5 per query) are re-scored with

@@ -78,6 +78,9 @@ def test_version_and_argument_errors_without_a_gpu(library):
     assert L.deva_affinity_force_shape(2) == 0
     assert L.deva_affinity_default_splits(1620, 1620) == 26  # per-wave lists: <= 64 tokens per range, no filtering needed
     assert L.deva_affinity_force_shape(9) != 0 and L.deva_affinity_force_shape(0) == 0
+    for gone in (1, 3, 5, 6, 7):  # the A/B variants of round 2 are refused in every build
+        assert L.deva_affinity_force_shape(gone) != 0
+        assert L.deva_affinity_force_shape(0) == 0 and L.deva_affinity_default_splits(1620, 1620) == 3
 
 
 def test_read_policy_and_scratch_sizes_are_host_side():

@@ -245,16 +245,13 @@ def test_fp16_prefilter_shard_keys_equal_the_fp32_select():
     assert torch.equal(new[1], old[1]) and torch.equal(new[0][:, :k], old[0][:, :k])
 
 
-@pytest.mark.parametrize('shape', [1, 2, 3, 4, 5, 6, 7, 8])
+@pytest.mark.parametrize('shape', [2, 4, 8])
 def test_every_kernel_shape_gives_the_same_result(shape):
-    """the kernel shapes of deva_affinity_topk (per-wave / workgroup-shared lists, one / two workgroups per CU,
-    shared key tiles, early / late prefetch) forced in turn: identical indices, weights and usage counters as the
-    automatic choice, on a bank with a long-term part, ragged sizes and enough tokens for several prune rounds"""
+    """the kernel shapes of deva_affinity_topk (per-wave lists; workgroup-shared lists on four / eight waves) forced in
+    turn: identical indices, weights and usage counters as the automatic choice, on a bank with a long-term part, ragged
+    sizes and enough tokens for several prune rounds"""
     from deva.hip import check, lib
     cases = [(5000, 1620, 2.0, 30, 1200), (999, 129, 0.2, 7, 0), (20000, 257, 1.0, 30, 333), (33, 1, 1.0, 30, 0)]
-    if lib().deva_affinity_force_shape(shape) != 0:
-        lib().deva_affinity_force_shape(0)
-        pytest.skip('A/B variant of probe builds (make PROBES=1); the product library carries shapes 2, 4 and 8')
     try:
         lib().deva_affinity_force_prefilter(0)  # the shapes belong to the fp32 kernels
         for n, hw, scale, k, n_long in cases:
@@ -268,6 +265,39 @@ def test_every_kernel_shape_gives_the_same_result(shape):
     finally:
         lib().deva_affinity_force_shape(0)
         lib().deva_affinity_force_prefilter(1)
+
+
+# bit-identity across differently shaped launches is a property of the kernels (fixed accumulation order per score),
+# not of the PyTorch emulation the dry run substitutes (a float32 BLAS product depends on its blocking)
+kernel_property = pytest.mark.skipif(os.environ.get('DEVA_TEST_DRYRUN') == '1',
+                                     reason='checks a property of the HIP kernels; the dry run emulates them')
+
+
+@kernel_property
+@pytest.mark.parametrize('k', [30, 32, 1])
+def test_every_owner_of_the_tail_gives_the_same_read(k):
+    """the exact tail of a read (sort the k keys, exp, sequential sum, divide, usage counters) is shared by the merge
+    kernel of the fp32 lists, the re-score kernel of the fp16 pre-filter and the dense kernel: the same read through the
+    three must agree bit for bit.  Smallest sizes at which the pre-filter policy engages, ragged against 32 and 64."""
+    from deva.hip import lib
+    n, n_long, hw = 4200, 1000, 2001
+    mk, ms, qk, qe = synth.affinity_inputs(n, hw, seed=n + hw + k)
+    assert lib().deva_affinity_prefilter_enabled(n, hw, k) == 1, 'shape below the library\'s pre-filter policy'
+    try:
+        lib().deva_affinity_force_shape(0)
+        lib().deva_affinity_force_prefilter(0)
+        lists = _run(mk, ms, qk, qe, k, n_long)
+        lib().deva_affinity_force_prefilter(1)
+        pre = _run(mk, ms, qk, qe, k, n_long)
+        assert ops.affinity_last_read_flag(dev()) == 0, 'the pre-filter fell back: the merge kernel produced this read'
+        dense = _run_dense(mk, ms, qk, qe, k, n_long)
+    finally:
+        lib().deva_affinity_force_shape(0)
+        lib().deva_affinity_force_prefilter(1)
+    for owner, got in (('pre-filter', pre), ('dense', dense)):
+        assert torch.equal(got[0], lists[0]), f'{owner}: indices differ from the fp32 lists'
+        assert torch.equal(torch.nan_to_num(got[1], nan=-1.0), torch.nan_to_num(lists[1], nan=-1.0)), f'{owner}: weights'
+        assert torch.equal(got[2], lists[2]), f'{owner}: usage counters'
 
 
 def test_determinism_and_usage_clear():
@@ -299,12 +329,6 @@ def test_readout_two_segments_ragged():
     out = torch.empty(cv, hw, device=dev())
     ops.readout_sparse(to_dev(idx), to_dev(w), to_dev(vl), n_long, to_dev(vw), out)
     assert max_err(out, want) <= 1e-4
-
-
-# bit-identity across differently shaped launches is a property of the kernels (fixed accumulation order per score),
-# not of the PyTorch emulation the dry run substitutes (a float32 BLAS product depends on its blocking)
-kernel_property = pytest.mark.skipif(os.environ.get('DEVA_TEST_DRYRUN') == '1',
-                                     reason='checks a property of the HIP kernels; the dry run emulates them')
 
 
 @kernel_property

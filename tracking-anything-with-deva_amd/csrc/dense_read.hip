@@ -2,7 +2,7 @@
 // memory_utils.py:48-76): p[n][q] = exp(s[n][q] - max_n s[.][q]) / sum_n exp(s[n][q] - max), the usage
 // counters usage[n] = sum_q p[n][q], and the read-out out[o][c][q] = sum_n V_o[n][c] * p[n][q] of every object.
 //
-// Scores are the natural-order fp32 values of affinity.hip (affinity_topk_kernel / affinity_pf_rescore_kernel):
+// Scores are the natural-order fp32 values of the list kernels (affinity_topk_kernel / affinity_pf_rescore_kernel):
 // A = sum_c mk^2 qe and B = sum_c mk (qk qe) as v_mfma_f32_32x32x2_f32 chains over the channels in natural order,
 // bsq in ATen's summation order, v = ((2B - A) - bsq) * (ms / 8).  Four kernels per read, none of which holds the
 // N x HW matrix whole:
@@ -16,22 +16,16 @@
 //                         operand (channels x tokens), the chunk's p rows the B operand, both staged through LDS.
 //                         Every output sums the tokens in the virtual long-then-work order (32-token MFMA chains
 //                         added to a running total), so the result does not depend on where the segments split.
+// Also here: affinity_dense_kernel, the top-k read for 32 < k <= 64 (one kernel, at the end of the file).
 #include <math.h>
 
-#include "common.h"
+#include "affinity_common.h"
 
 #pragma clang fp contract(off)
 
 namespace deva {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef f32x4 f32x4_u __attribute__((aligned(4)));  // 16-B load from a dword-aligned address
-
-constexpr int CK = 64;
-constexpr int QT = 32;                   // queries per wave (MFMA N)
-constexpr int TOKT = 32;                 // tokens per score tile (MFMA M)
 constexpr int DR_WAVES = 4;
 constexpr int DR_QB = DR_WAVES * QT;     // queries per workgroup of the score kernels
 constexpr int DR_MAX_SPLITS = 64;        // token ranges of pass 1
@@ -42,51 +36,18 @@ constexpr int RO_QB = 64;                // read-out: queries per workgroup (two
 constexpr int RO_KT = 32;                // read-out: tokens per LDS stage
 constexpr int RO_VS = RO_CB + 32;        // LDS row strides: rows 2k and 2k+1 of an MFMA operand on opposite bank halves
 constexpr int RO_PS = RO_QB + 32;
-constexpr float TWO40 = 1099511627776.0f;
-
-#define DR_WAVE_FENCE()                                     \
-  do {                                                      \
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); \
-    __builtin_amdgcn_wave_barrier();                        \
-  } while (0)
-
-struct DrBank {
-  const float* key_long;
-  const float* shr_long;
-  int n_long;
-  const float* key_work;
-  const float* shr_work;
-  int n_total;
-};
-
-// B operands of query q for MFMA t (channel 2t + half) and bsq, exactly as affinity_topk_kernel forms them
-__device__ __forceinline__ float load_query(const float* __restrict__ qk, const float* __restrict__ qe, int hw, int q,
-                                            int half, float (&bqe)[CK / 2], float (&bqk)[CK / 2]) {
-  float bs[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int t = 0; t < CK / 2; ++t) {
-    const float e0 = qe[(int64_t)(2 * t) * hw + q], e1 = qe[(int64_t)(2 * t + 1) * hw + q];
-    const float k0 = qk[(int64_t)(2 * t) * hw + q], k1 = qk[(int64_t)(2 * t + 1) * hw + q];
-    bs[t >> 3] += e0 * (k0 * k0);
-    bs[t >> 3] += e1 * (k1 * k1);
-    bqe[t] = half ? e1 : e0;
-    bqk[t] = half ? (k1 * e1) : (k0 * e0);
-  }
-  return ((bs[0] + bs[1]) + bs[2]) + bs[3];
-}
 
 // accumulator row r of a 32x32 MFMA block in lane half `half` <-> row (r & 3) + 8 (r >> 2) + 4 half of the block
 __device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // scores of the 32 tokens n_base.. against the wave's 32 queries: lane (l31, half) receives v[r] for query l31 and
 // token n_base + acc_row(r, half).  msl: this wave's 32-float LDS row.
-__device__ __forceinline__ void score_tile(const DrBank& b, int n_base, int lane, const float (&bqe)[CK / 2],
+__device__ __forceinline__ void score_tile(const Bank& b, int n_base, int lane, const float (&bqe)[CK / 2],
                                            const float (&bqk)[CK / 2], float bsq, float* msl, float (&v)[16]) {
   const int l31 = lane & 31, half = lane >> 5;
   const int n_mine = min(n_base + l31, b.n_total - 1);
-  const bool is_long = n_mine < b.n_long;
-  const float* krow = is_long ? (b.key_long + (int64_t)n_mine * CK) : (b.key_work + (int64_t)(n_mine - b.n_long) * CK);
-  const float ms = is_long ? b.shr_long[n_mine] : b.shr_work[n_mine - b.n_long];
+  float ms;
+  const float* krow = bank_row(b, n_mine, &ms);
   // channel 2t + half of this lane's token: the upper half-lanes read one float later (see affinity_topk_kernel)
   const float* shifted = krow + half;
   float a_op[CK / 2];
@@ -100,7 +61,7 @@ __device__ __forceinline__ void score_tile(const DrBank& b, int n_base, int lane
   a_op[CK / 2 - 2] = half ? xl[1] : xl[0];
   a_op[CK / 2 - 1] = half ? xl[3] : xl[2];
   if (lane < TOKT) msl[lane] = ms * 0.125f;  // 1/sqrt(CK) folded in (exact)
-  DR_WAVE_FENCE();
+  DEVA_COMPILER_FENCE();
   f32x16 accA, accB;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -123,11 +84,11 @@ __device__ __forceinline__ void score_tile(const DrBank& b, int n_base, int lane
       v[r] = (((accB[r] + accB[r]) - accA[r]) - bsq) * m[i];  // == ((-A + 2B) - bsq) * ms / 8, every step rounded
     }
   }
-  DR_WAVE_FENCE();  // the next tile rewrites msl
+  DEVA_COMPILER_FENCE();  // the next tile rewrites msl
 }
 
 struct DrStatsArgs {
-  DrBank bank;
+  Bank bank;
   const float* qk;
   const float* qe;
   int hw;
@@ -194,7 +155,7 @@ __global__ __launch_bounds__(256) void dense_finish_kernel(const float2* __restr
 }
 
 struct DrProbsArgs {
-  DrBank bank;
+  Bank bank;
   const float* qk;
   const float* qe;
   int hw;
@@ -388,6 +349,111 @@ DrPlan dense_plan(int n_total, int hw) {
 
 bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15u) == 0; }
 
+// ------------------------------------------------------------------ dense top-k read (32 < k <= 64)
+// The list kernels of affinity.hip size their per-range hand-over for k <= K_MAX = 32.  For the rare larger top_k
+// (eval_args.py:40 leaves it free) the read runs on this one kernel: lane = query (64 queries per one-wave workgroup,
+// query operands in registers), the bank streams through wave-uniform rows, every score is score_fp32 -- the
+// natural-order fp32 FMA chain affinity_pf_rescore_kernel runs (bit-identical scores, hence the same selection as the
+// list kernels for any k both can serve) --, and each lane keeps its k best (score, ~token) keys in LDS: unsorted,
+// smallest tracked, replaced on insert (~k ln(N/k) inserts per query).  Every query finishes like
+// affinity_finalize_kernel (an inline copy of the shared tail of affinity_common.h).  VALU-bound: 192 instructions per (token, query); ~4 ms at
+// N = 10 000 x 8 160 queries -- a correct path, not a fast one.
+constexpr int DK_MAX = 64;
+
+struct DenseArgs {
+  Bank bank;
+  const float* qk;
+  const float* qe;
+  int hw, k;
+  int32_t* idx;
+  float* weight;
+  unsigned long long* usage_fix;
+};
+
+__global__ __launch_bounds__(64) void affinity_dense_kernel(const DenseArgs p) {
+  __shared__ uint64_t s_list[DK_MAX][64];  // [entry][query lane]
+  __shared__ uint64_t s_sort[64];
+  const int lane = threadIdx.x;
+  const int q0 = blockIdx.x * 64;
+  const int qq = min(q0 + lane, p.hw - 1);
+  const int k = p.k, n = p.bank.n_total;
+  float qe[CK], qp[CK];
+  float bs[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // bsq in ATen's summation order (see load_query)
+#pragma unroll
+  for (int c = 0; c < CK; ++c) {
+    const float ev = p.qe[(int64_t)c * p.hw + qq], kv = p.qk[(int64_t)c * p.hw + qq];
+    qe[c] = ev;
+    qp[c] = kv * ev;
+    bs[c >> 4] += ev * (kv * kv);
+  }
+  const float bsq = ((bs[0] + bs[1]) + bs[2]) + bs[3];
+
+  uint64_t kmin = ~0ull;
+  int pmin = 0;
+  for (int t = 0; t < n; ++t) {  // t is wave-uniform: the row and its shrinkage are scalar loads
+    float ms;
+    const float* row = bank_row(p.bank, t, &ms);
+    // mirrors score_fp32 (affinity_common.h), inline: through the helper this VALU-bound loop measured 0.8 % slower
+    float accA = 0.0f, accB = 0.0f;
+#pragma unroll
+    for (int c = 0; c < CK; ++c) {
+      const float a = row[c];
+      accA = __builtin_fmaf(a * a, qe[c], accA);
+      accB = __builtin_fmaf(a, qp[c], accB);
+    }
+    const float v = (((accB + accB) - accA) - bsq) * (ms * 0.125f);
+    const uint64_t key = ((uint64_t)orderable(v) << 32) | (uint64_t)(~(uint32_t)t);
+    if (t < k) {  // (uniform) the first k tokens fill the list
+      s_list[t][lane] = key;
+      if (key < kmin) {
+        kmin = key;
+        pmin = t;
+      }
+    } else if (key > kmin) {
+      s_list[pmin][lane] = key;
+      kmin = ~0ull;
+      for (int e = 0; e < k; ++e) {
+        const uint64_t o = s_list[e][lane];
+        if (o < kmin) {
+          kmin = o;
+          pmin = e;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- per query of the tile: mirrors rank_sort_k + softmax_usage_tail (affinity_common.h), inline: through the helpers
+  // this kernel measured 0.3 % slower, outside the parent's spread (profiles/HISTORY.md)
+  const bool live = lane < k;
+  for (int j = 0; j < 64 && q0 + j < p.hw; ++j) {
+    const int q = q0 + j;
+    const uint64_t cand = live ? s_list[live ? lane : 0][j] : 0ull;
+    int rank = 0;
+    for (int r = 0; r < k; ++r) {
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)cand, r);
+      const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(cand >> 32), r);
+      rank += ((((uint64_t)hi << 32) | lo) > cand) ? 1 : 0;
+    }
+    __syncthreads();  // (one wave: orders the LDS traffic of consecutive queries)
+    if (live) s_sort[rank] = cand;
+    __syncthreads();
+    const uint64_t mine = live ? s_sort[lane] : 0ull;  // lane r holds the r-th best
+    const float score = from_orderable((uint32_t)(mine >> 32));
+    const uint32_t token = ~(uint32_t)mine;
+    const float ex = live ? expf(score) : 0.0f;
+    float sum = 0.0f;
+    for (int r = 0; r < k; ++r)  // sequential, like torch.sum over the sorted top-k
+      sum += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ex), r));
+    const float w = ex / sum;
+    if (live) {
+      p.idx[(int64_t)q * k + lane] = (int32_t)token;
+      p.weight[(int64_t)q * k + lane] = w;
+      if (p.usage_fix && w == w) atomicAdd(&p.usage_fix[token], (unsigned long long)(w * TWO40));
+    }
+  }
+}
+
 }  // namespace
 }  // namespace deva
 
@@ -432,13 +498,7 @@ extern "C" int deva_dense_read(const float* key_long, const float* shr_long, int
   DEVA_REQUIRE(aligned16(probs), "deva_dense_read: probs must be 16-B aligned");
   hipStream_t st = (hipStream_t)stream;
   uint8_t* base = reinterpret_cast<uint8_t*>(scratch);
-  DrBank b;
-  b.key_long = key_long ? key_long : key_work;
-  b.shr_long = shr_long ? shr_long : shr_work;
-  b.n_long = n_long;
-  b.key_work = key_work ? key_work : key_long;
-  b.shr_work = shr_work ? shr_work : shr_long;
-  b.n_total = (int)n_total;
+  const Bank b = make_bank(key_long, shr_long, n_long, key_work, shr_work, n_total);
   float2* part = reinterpret_cast<float2*>(base + L.off_part);
   float2* stats = reinterpret_cast<float2*>(base + L.off_stats);
 
@@ -501,4 +561,29 @@ extern "C" int deva_dense_read(const float* key_long, const float* shr_long, int
     }
   }
   return 0;
+}
+
+extern "C" int deva_affinity_dense(const float* key_long, const float* shr_long, int n_long, const float* key_work,
+                                   const float* shr_work, int n_work, const float* qk, const float* qe, int hw, int k,
+                                   int32_t* idx, float* weight, uint64_t* usage_fix, void* stream) {
+  DEVA_REQUIRE(qk && qe && idx && weight && hw > 0, "deva_affinity_dense: bad args");
+  DEVA_REQUIRE(n_long >= 0 && n_work >= 0, "deva_affinity_dense: negative bank size");
+  DEVA_REQUIRE(n_long == 0 || (key_long && shr_long), "deva_affinity_dense: null long-term segment");
+  DEVA_REQUIRE(n_work == 0 || (key_work && shr_work), "deva_affinity_dense: null working segment");
+  DEVA_REQUIRE(k >= 1 && k <= DK_MAX, "deva_affinity_dense: k=%d unsupported (1..%d)", k, DK_MAX);
+  const int64_t n_total = (int64_t)n_long + n_work;
+  DEVA_REQUIRE(n_total >= k, "deva_affinity_dense: selected index k out of range (bank has %lld tokens, k=%d)",
+               (long long)n_total, k);
+  DEVA_REQUIRE(n_total < (1ll << 31) - 64, "deva_affinity_dense: bank too large");
+  DenseArgs a;
+  a.bank = make_bank(key_long, shr_long, n_long, key_work, shr_work, n_total);
+  a.qk = qk;
+  a.qe = qe;
+  a.hw = hw;
+  a.k = k;
+  a.idx = idx;
+  a.weight = weight;
+  a.usage_fix = (unsigned long long*)usage_fix;
+  hipLaunchKernelGGL(affinity_dense_kernel, dim3((unsigned)ceil_div(hw, 64)), dim3(64), 0, (hipStream_t)stream, a);
+  return check_launch("deva_affinity_dense");
 }
