@@ -2,6 +2,7 @@
 // rocprofv3 --pmc pass over it costs seconds).
 //
 //   convlab [--libs a.so,b.so,...] [--only substr] [--iters N] [--set frame480|big|small] [--check]
+//           [--wino | --wino_all] [--rounds N [--spread]]     (all options: README.md)
 //
 // Every library is dlopen'ed and driven through the C ABI of include/deva_hip.h.  The layer list is the 480p /
 // 5-object frame of bench.py (profiles/r03c/conv_layers_480p5.json) with the number of calls per frame, so
@@ -137,7 +138,7 @@ int main(int argc, char** argv) {
   std::string libs = "tracking-anything-with-deva_amd/deva/hip/libdeva_hip.so";
   std::string only, set = "frame480", shapes;
   int iters = 20;
-  bool check = false, csv = false, stamps = false, amp = false, split = false, overflow = false, zero_in = false, wino = false;
+  bool check = false, csv = false, stamps = false, amp = false, split = false, overflow = false, zero_in = false, wino = false, wino_all = false, spread = false;
   int keepalive_ms = 0;
   int rounds = 1;
   double warm_ms = 15.0, time_ms = 20.0;
@@ -154,6 +155,8 @@ int main(int argc, char** argv) {
     else if (a == "--stamps") stamps = true;
     else if (a == "--amp") amp = true;  // fp16 operands on every library but the first (which stays the fp32 reference)
     else if (a == "--wino") wino = true;  // fp32 Winograd on every library but the first
+    else if (a == "--wino_all") wino = wino_all = true;  // ... and on the first: Winograd against Winograd (--check: d0.0e+00 = bit-identical)
+    else if (a == "--spread") spread = true;  // min - max of the rounds behind the median
     else if (a == "--split") split = true;  // hi/lo fp16 split (fp32-accurate) on every library but the first
     else if (a == "--zero_in") zero_in = true;  // all-zero activations (power probe: operand switching activity)
     else if (a == "--overflow") overflow = true;  // one input element beyond the fp16 range: the split path must fall back
@@ -335,7 +338,7 @@ int main(int argc, char** argv) {
           d.split_flag = (int32_t*)dev_alloc_guarded(4, keep);  // zeroed
         }
       }
-      if (wino && li > 0 && l.packwi && ly.k == 3 && ly.stride == 1) {
+      if (wino && (li > 0 || wino_all) && l.packwi && ly.k == 3 && ly.stride == 1) {
         const int64_t nw = l.packwi(h_w.data(), nullptr, ly.cout, cin);
         if (nw > 0) {
           std::vector<float> ww(nw);
@@ -444,6 +447,7 @@ int main(int argc, char** argv) {
       frame_us[li] += us * ly.calls;
       (ly.set == 1 ? big_us : small_us)[li] += us * ly.calls;
       if (csv) printf("\ncsv,%s,%zu,%.2f,%.3f,%.1f", ly.name, li, us, gf, ly.calls);
+      else if (spread) printf(" | %8.1f us [%7.1f - %7.1f]%s", us, v.front(), v.back(), tails[li].c_str());
       else printf(" | %8.1f us %6.1f TF%s", us, gf / us * 1e3, tails[li].c_str());
     }
     printf("\n");

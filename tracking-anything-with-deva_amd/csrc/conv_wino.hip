@@ -14,7 +14,8 @@
 // inside an image), K = input channels.  A workgroup = 8 waves = 64 output channels x 64 tiles; K advances in steps of 8
 // channels through two double-buffered LDS tiles (2 x 2 x 32 KB):
 //   * transformed weights U (deva_conv_pack_wino: [c/8][p][c%2][cout_pad][c%8/2], i.e. the four k values a lane feeds to the
-//     four MFMAs of a position are one 16-byte read) go global -> LDS as they are;
+//     four MFMAs of a position are one 16-byte read) go global -> LDS as they are, by LDS-DMA (buffer_load_dwordx4 ... lds:
+//     the tile's image is lane-linear per wave, 64 lanes x 16 bytes = 1 KB contiguous -- no registers, no LDS stores);
 //   * activations: thread (channel, tile) loads the 4x4 patch of its tile (four unaligned 16-byte buffer loads from
 //     guard-banded inputs; rows outside the image are out-of-range offsets and come back as zeros), applies ReLU-on-load
 //     and B^T d B in registers (16 packed additions) and writes the 16 transformed values as [p][k parity][k/2][tile] (a wave
@@ -23,6 +24,7 @@
 // Output stage: the position sums of a (channel, tile) pair sit in ONE lane (same register index of the accumulators):
 // A^T M A is additions in registers, then bias / residual / activation and two 8-byte stores per output channel.
 #include <cstdlib>
+#include <type_traits>
 
 #include "conv_args.h"
 
@@ -52,9 +54,19 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
   return r;
 }
 
+#ifdef DEVA_CONV_PROBES  // timing-only ablations of the K step (results are wrong), DEVA_WINO_ABLATE: 1 staging stores, 2 activation loads, 4 barrier, 8 weight DMA
+#define WINO_ABL(bit) (p.ablate & (bit))
+#else
+#define WINO_ABL(bit) false
+#endif
+
 constexpr int WM = 64, WN = 64;  // output channels x tiles of a workgroup
 constexpr int KC = 8;            // channels per K step
 constexpr int TILE_FLOATS = 16 * 2 * 64 * 4;  // one operand tile of a K step: [p][k parity][row / column][4]
+
+template <int N>
+__device__ __forceinline__ constexpr std::integral_constant<int, (N ^ 1)> flip_buf(std::integral_constant<int, N>) { return {}; }
+__device__ __forceinline__ int flip_buf(int b) { return b ^ 1; }
 
 struct WinoArgs {
   const float* in0;
@@ -73,6 +85,7 @@ struct WinoArgs {
   float* out;
   int blocks_m;
   int by_tiles;  // grid numbered XCD-major (see the kernel)
+  int ablate;    // `make PROBES=1` builds only (DEVA_WINO_ABLATE), 0 otherwise
 };
 
 
@@ -86,12 +99,35 @@ struct WinoArgs {
 // Measured against the 4-wave form on one box (tools/convlab --wino, us): up_8_4 256 -> 256 at 120x216 x5 725 -> 667 (742 ->
 // 675 with a residual, 786 -> 659 with ReLU-on-load), GRU 1024 -> 1536 1 011 -> 925, fuser 512 -> 512 175 -> 161, up_16_8
 // 363 -> 315 / 348 -> 319.
-// Staging: thread = (ONE channel = wave, tile = lane): four patch rows, 16 packed additions, 16 LDS stores; four 16-byte
-// weight chunks.  One register set: the loads of step s + 1 go out at the top of step s and are transformed / stored behind
-// its MFMAs -- the other wave of the SIMD covers what the wait costs.  Measured and dropped: the two waves of a SIMD running a
-// step in opposite order, one staging first and one last (0 - 5 % slower).  RELU / RES are compile-time: ReLU-on-load is ONE instruction per
-// element (median of x, 0, limit: limit = +inf, or 0 for a masked column -- no NaN canonicalisation in front of it as with
-// v_max), and with it the staging pays behind the third MFMA group instead of the last (2 % on those layers).
+// Staging: thread = (ONE channel = wave, tile = lane): four patch rows, 16 packed additions, 16 LDS stores; the weights
+// are four LDS-DMA loads per thread and step.  RELU / RES are compile-time: ReLU-on-load is ONE instruction per element
+// (median of x, 0, limit: limit = +inf, or 0 for a masked column -- no NaN canonicalisation in front of it as with v_max).
+// The K pipeline (what each of its parts bought is measured in ONE lab call against the previous form, `tools/convlab
+// --wino_all --check --rounds 7 --spread`, medians in us for up_8_4 256 -> 256 at 120x216 x5 / GRU 1024 -> 1536 at 30x54 x5 /
+// fuser 512 -> 512 at 30x54 x5; every form bit-identical to the previous one, d0.0e+00 on all layers):
+//   previous form   671 / 917 / 160   run-time LDS buffer index, weights through 16 registers + 4 ds_write_b128, ONE
+//                                     activation register set loaded at the top of step s and staged in front of its barrier
+//   (1) K loop unrolled by two over compile-time buffers (an exit after either half: odd counts and one step need no
+//       second body, the accumulators are never copied): every LDS address is base + immediate, 46 -> 40 VALU per step.
+//       Alone 673 / 924 / 161 -- nothing; under (2) + (3) it is worth 3.3 % (658 / 896 / 156 without it): kept.
+//   (2) weights by LDS-DMA, issued behind the barrier for the tile TWO steps ahead: 642 / 876 / 152 (-4.4 %).  228 -> 210
+//       VGPRs.  The loop's barrier is a raw s_barrier behind `s_waitcnt vmcnt(4) lgkmcnt(0)`: the DMA is the oldest
+//       vector-memory operation in flight, the four activation loads behind it stay in flight across the barrier.
+//   (3) activations staged BEHIND the barrier (tile s + 2 into the buffers of tile s, from loads issued a step earlier;
+//       still one register set: the loads of tile s + 3 go out right after the stores): 638 / 872 / 151 (-0.5 % more; the
+//       median lies below the minimum of (2) on every layer).  194 / 198 VGPRs.
+//   dropped: waves 0 - 3 staging behind the barrier and waves 4 - 7 in front of it (the stagger): 725 / 966 / 170, 13 %
+//       SLOWER than (3) -- both staging bodies in every step, and the late waves' loads are waited for at the next use.
+//   not built: a second activation register set (one suffices once the stores come before the re-issue), the output stage on
+//       eight waves.
+// Resources (hipcc -O3, -Rpass-analysis=kernel-resource-usage), previous form -> now: VGPRs 227 / 227 / 230 / 230 -> 194 /
+// 194 / 198 / 198 (<RELU, RES> = ff / ft / tf / tt), LDS 131 072 bytes, occupancy 2, no spills, no scratch.  One wave's
+// step <false, false>: 32 MFMA, 46 -> 30 VALU (16 v_pk_add, 9 v_cndmask, 5 v_add for the load offsets), 36 -> 32 LDS
+// instructions (the 4 ds_write_b128 are gone), 8 VMEM, 19 -> 14 s_waitcnt.
+// On counters over the 480p / 5-object frame (profiles/r07/pmc/): matrix pipe 0.656 -> 0.688 busy, VALU instructions
+// per launch -18.8 %, MFMA instructions and HBM traffic unchanged; bench.py 170.1 -> 175.8 FPS on one box.
+// `make PROBES=1`: DEVA_WINO_ABLATE switches parts of the step off for timing (1 staging stores, 2 activation loads, 4
+// barrier, 8 weight DMA; results are wrong).  On up_8_4 (probe build 677 us): -13 / -54 / -55 / -28 us, all four -104.
 // Output stage: A^T M A is linear in the rows of M, so each half reduces its own rows to a partial 2x2 output in registers,
 // the ph = 1 waves hand theirs over through LDS (64 KB, the weight tiles' space) and the ph = 0 waves add, apply bias /
 // residual / activation and store.  Residual and bias of eight channels are fetched together, up front: a load issued
@@ -104,8 +140,10 @@ struct WinoArgs {
 // their cout blocks, one after the other: an activation tile enters one L2, not blocks_m of them (1 - 4 %).
 template <bool RELU, bool RES>
 __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
-  __shared__ __attribute__((aligned(16))) float sA[2][TILE_FLOATS];
-  __shared__ __attribute__((aligned(16))) float sB[2][TILE_FLOATS];
+  // ONE array, the weight tiles first: their LDS-DMA destinations (the M0 base of a wave's 1 KB) stay below 64 KB
+  __shared__ __attribute__((aligned(16))) float smem[4 * TILE_FLOATS];
+#define sA(b) (smem + (b) * TILE_FLOATS)
+#define sB(b) (smem + (2 + (b)) * TILE_FLOATS)
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -154,12 +192,21 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
     for (int r = 0; r < 16; ++r) acc[q][r] = 0.0f;
 
   const int ksteps = p.ctot / KC;
-  f32x4 ra[4], rb[4];
-  auto load_step = [&](int s) {
+  f32x4 rb[4];
+  // weights of step s -> sA(buf).  LDS-DMA: a wave's 64 lanes x 16 bytes land at (wave-uniform base) + lane * 16, which IS
+  // the tile's image ((tid + 512 i) * 16 bytes); no registers, no LDS store instructions
+  auto load_w = [&](int s, auto bufc) {
+    const int buf = bufc;
+    if (WINO_ABL(8)) return;
     const float* ub = p.u + ((int64_t)s * 32 * p.cout_pad + m0) * 4;
     const __amdgpu_buffer_rsrc_t ru = make_rsrc(ub, 0x7fffffff);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) ra[i] = buf_load4(ru, aoff, i * astride);
+    for (int i = 0; i < 4; ++i)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ru, (__attribute__((address_space(3))) void*)(sA(buf) + (wave * 64 + 512 * i) * 4), 16, aoff,
+                                               i * astride, 0, 0);
+  };
+  auto load_act = [&](int s) {
+    if (WINO_ABL(2)) return;
     const int c = s * KC;
     const bool first = c < p.c0;
     const float* base = (first ? p.in0 + (int64_t)c * HW : p.in1 + (int64_t)(c - p.c0) * HW) - 4;
@@ -168,11 +215,9 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) rb[i] = buf_load4(rx, pb + poff[i], 0);
   };
-  auto store_step = [&](int buf) {
-    float* a = sA[buf];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(a + (tid + 512 * i) * 4) = ra[i];
-    float* bdst = sB[buf] + (sh * 4 + sm) * 64 + st;  // position q at + q * 8 * 64
+  auto stage_act = [&](auto bufc) {  // rb -> ReLU-on-load, B^T d B -> sB(buf)
+    const int buf = bufc;
+    float* bdst = sB(buf) + (sh * 4 + sm) * 64 + st;  // position q at + q * 8 * 64
     f32x2 dl[4], dr[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -199,6 +244,10 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
       f32x2 lo, hi;  // (w0 - w2, w1 + w2), (w2 - w1, w1 - w3) of the row (w0, w1 | w2, w3)
       asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(lo) : "v"(wl[i]), "v"(wr[i]));
       asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[1,0]" : "=v"(hi) : "v"(wr[i]), "v"(wl[i]));
+      if (WINO_ABL(1)) {
+        asm volatile("" ::"v"(lo), "v"(hi));
+        continue;
+      }
       bdst[(4 * i + 0) * 8 * 64] = lo[0];
       bdst[(4 * i + 1) * 8 * 64] = lo[1];
       bdst[(4 * i + 2) * 8 * 64] = hi[0];
@@ -208,9 +257,12 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
 
   // fragments of position 8 ph + j: A = 16 bytes (the four k values of the lane's channel and k parity), B = four floats
   f32x4 fa[2][2], fb[2][2];
-  auto read_frag = [&](int buf, int set, int g) {
-    const float* a_rd = sA[buf] + ((8 * ph) * 2 * 64 + half * 64 + wm * 32 + l31) * 4;
-    const float* b_rd = sB[buf] + ((8 * ph) * 2 + half) * 4 * 64 + wn * 32 + l31;
+  const float* a_rd0 = sA(0) + ((8 * ph) * 2 * 64 + half * 64 + wm * 32 + l31) * 4;
+  const float* b_rd0 = sB(0) + ((8 * ph) * 2 + half) * 4 * 64 + wn * 32 + l31;
+  auto read_frag = [&](auto bufc, int set, int g) {
+    const int buf = bufc;
+    const float* a_rd = a_rd0 + buf * TILE_FLOATS;
+    const float* b_rd = b_rd0 + buf * TILE_FLOATS;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int q = 2 * g + j;
@@ -226,32 +278,75 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
       for (int j = 0; j < 2; ++j)
         acc[2 * g + j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[set][j][e], fb[set][j][e], acc[2 * g + j], 0, 0, 0);
   };
-  // A step runs ACROSS the workgroup barrier: the fragments of its last two positions are in registers before the barrier,
-  // their MFMAs are issued behind it and cover the LDS latency of the next step's first fragments (both waves of a SIMD
-  // arrive at the barrier together: without this the matrix pipe idles for a round trip at every step)
-  load_step(0);
-  store_step(0);
-  __syncthreads();
-  read_frag(0, 0, 0);
-  for (int s = 0; s < ksteps; ++s) {
-    const int buf = s & 1;
-    const bool more = s + 1 < ksteps;
-    if (more) load_step(s + 1);
+  // Workgroup barrier of the K loop: a raw s_barrier behind explicit waits (a __syncthreads() with a DMA outstanding drains
+  // vmcnt(0)).  lgkmcnt(0): this wave's LDS stores of the next tile's activations.  vmcnt(4): its weight DMA of the tile
+  // that is read behind the barrier -- the DMA is the OLDEST vector-memory operation in flight, and exactly the four
+  // activation loads issued after it are younger; they stay in flight across the barrier.
+  auto wg_barrier = [&]() {
+    if (WINO_ABL(4)) return;
+    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  };
+  constexpr std::integral_constant<int, 0> B0{};
+  constexpr std::integral_constant<int, 1> B1{};
+
+  // One K step on buffer `buf` (compile time: every LDS address of the step is a base register + immediate).  It runs
+  // ACROSS the workgroup barrier: the fragments of its last two positions are in registers before the barrier, their MFMAs
+  // are issued behind it and cover the LDS latency of the next step's first fragments.
+  // Behind the barrier that ends step s, tile s + 2 goes into the buffers of tile s: the activations that were loaded a
+  // step ago are transformed and stored, THEN the weight DMA is issued (with a DMA in flight the compiler waits vmcnt(0)
+  // at the use of an ordinary load's result: here only those loads are outstanding), then the loads of tile s + 3 go out
+  // (ONE register set: rb is free again).  Nothing in a step waits for a load younger than a step.
+  // INVARIANT: the buffers of tile s are free behind that barrier ONLY because every wave has read its last fragments of
+  // tile s (position pair 3, register set 1) BEFORE it; nothing reads sA(buf) / sB(buf) until tile s + 2 is complete (the
+  // waits in front of the barrier that ends step s + 1).
+  // Tile 1 has no barrier to go behind: every wave stages it in front of the barrier of step 0, as the previous form of
+  // this kernel did for every tile (with ReLU-on-load behind the third MFMA group instead of the last: 2 % there).
+  auto step = [&](auto bufc, int s) {
+    const auto other = flip_buf(bufc);
+    const bool tile1 = s == 0 && ksteps > 1;
+    auto stage_tile1 = [&]() {
+      stage_act(other);
+      load_act(min(2, ksteps - 1));  // (always four loads behind a DMA: the barrier's counted wait)
+    };
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
-      read_frag(buf, (g + 1) & 1, g + 1);
+      read_frag(bufc, (g + 1) & 1, g + 1);
       multiply(g & 1, g);
-      if (RELU && g == 2 && more) store_step(buf ^ 1);
+      if (RELU && g == 2 && tile1) stage_tile1();
     }
-    if (!RELU && more) store_step(buf ^ 1);
-    __syncthreads();
-    if (more) read_frag(buf ^ 1, 0, 0);
+    if (!RELU && tile1) stage_tile1();
+    wg_barrier();
+    if (s + 1 < ksteps) read_frag(other, 0, 0);
+    if (s + 2 < ksteps) {
+      stage_act(bufc);
+      load_w(s + 2, bufc);
+      load_act(min(s + 3, ksteps - 1));
+    }
     multiply(1, 3);
+  };
+
+  load_act(0);
+  load_w(0, B0);
+  stage_act(B0);
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  read_frag(B0, 0, 0);
+  if (ksteps > 1) {
+    load_w(1, B1);
+    load_act(1);
   }
+  for (int s = 0;;) {  // unrolled by two with an exit after either half: odd counts and ksteps == 1 need no second body
+    step(B0, s);
+    if (++s == ksteps) break;
+    step(B1, s);
+    if (++s == ksteps) break;
+  }
+  // No DMA is in flight here (the last one, tile ksteps - 1, was waited for in front of the barrier of step ksteps - 2), but
+  // the exchange area below is the weight tiles' space: the wait is unconditional
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
   // ---- output stage.  Rows of M held by this half -> partial t0 = (A^T M)[0], t1 = (A^T M)[1], then the column pass:
   //   ph = 0: t0 = M0 + M1, t1 = M1;      ph = 1: t0 = M2, t1 = -M2 - M3
-  float* xch = sA[0] + (wq * 16 * 4) * 64 + lane;  // [quadrant][r][a * 2 + j][lane]: 64 KB = both weight tiles
+  float* xch = sA(0) + (wq * 16 * 4) * 64 + lane;  // [quadrant][r][a * 2 + j][lane]: 64 KB = both weight tiles
   const int n = n0 + wn * 32 + l31;
   const bool n_ok = n < p.n_tiles;
   if (ph == 1) {
@@ -343,6 +438,9 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
   }
 }
 
+#undef sA
+#undef sB
+
 }  // namespace
 
 // -> 0 launched, 1 launch error, -1 not eligible (the caller runs the direct kernels)
@@ -374,6 +472,14 @@ int launch_conv_wino(const ConvArgs& a, const float* u, hipStream_t st) {
   p.act = a.act;
   p.out = a.out;
   p.blocks_m = p.cout_pad / WM;
+  p.ablate = 0;
+#ifdef DEVA_CONV_PROBES
+  static const int ablate_probe = [] {
+    const char* e = getenv("DEVA_WINO_ABLATE");
+    return e ? atoi(e) : 0;
+  }();
+  p.ablate = ablate_probe;
+#endif
   p.by_tiles = (int64_t)batch * a.HW > 16ll * p.cout_pad;  // activation elements per channel > transformed weights per channel
 #if defined(DEVA_CONV_PROBES) || defined(DEVA_WINO_TUNE)  // (`make EXTRA=-DDEVA_WINO_TUNE`: the threshold alone, kernels as shipped)
   static const int min_blocks_probe = [] {
