@@ -60,6 +60,8 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
 #define WINO_ABL(bit) false
 #endif
 
+#define SCHED_PIN() __builtin_amdgcn_sched_barrier(0)  // nothing is scheduled across it
+
 constexpr int WM = 64, WN = 64;  // output channels x tiles of a workgroup
 constexpr int KC = 8;            // channels per K step
 constexpr int TILE_FLOATS = 16 * 2 * 64 * 4;  // one operand tile of a K step: [p][k parity][row / column][4]
@@ -118,21 +120,44 @@ struct WinoArgs {
 //       median lies below the minimum of (2) on every layer).  194 / 198 VGPRs.
 //   dropped: waves 0 - 3 staging behind the barrier and waves 4 - 7 in front of it (the stagger): 725 / 966 / 170, 13 %
 //       SLOWER than (3) -- both staging bodies in every step, and the late waves' loads are waited for at the next use.
-//   not built: a second activation register set (one suffices once the stores come before the re-issue), the output stage on
-//       eight waves.
+//   not built: a second activation register set (one suffices once the stores come before the re-issue).
+// The compiled step IS the designed step only with the schedule pinned (SCHED_PIN = sched_barrier(0) around every fragment
+// read group, MFMA group, the barrier and the staging block; check the -S listing, not the source).  Without the pins the
+// register allocator folds the two fragment sets into one and the scheduler sinks each read group below the MFMAs in front
+// of it: prefetch distance zero, pair 2 behind the barrier, twelve LDS reads drained at the barrier by both waves of a
+// SIMD at once.  Pinned: the reads of pair g + 1 go out in front of the 8 MFMAs of pair g into the other set and are
+// waited for a whole MFMA group later (lgkmcnt(9) / (7) / (6)), the MFMAs of pair 2 are issued in front of the barrier,
+// behind it come the next tile's first fragments, the staging block, then the MFMAs of pair 3.  The barrier's wait is
+// the s_waitcnt BUILTIN, not text inside the asm statement: the compiler cannot see a wait in inline assembly and put
+// its own lgkmcnt(3) / (1) / (0) in front of the MFMAs of pair 3 -- a wait for the staging stores and the next tile's
+// fragments just issued, i.e. one exposed LDS round trip per step exactly where the MFMAs were meant to cover it.
+// Loop overhead: the four load offsets of both sources are built once, the descriptor base advances by a scalar add per
+// step and the switch from in0 to in1 is a branch taken once (the 5 v_add + 1 v_cndmask and ~13 scalar instructions of
+// every step are gone).
 // Resources (hipcc -O3, -Rpass-analysis=kernel-resource-usage), previous form -> now: VGPRs 227 / 227 / 230 / 230 -> 194 /
 // 194 / 198 / 198 (<RELU, RES> = ff / ft / tf / tt), LDS 131 072 bytes, occupancy 2, no spills, no scratch.  One wave's
 // step <false, false>: 32 MFMA, 46 -> 30 VALU (16 v_pk_add, 9 v_cndmask, 5 v_add for the load offsets), 36 -> 32 LDS
-// instructions (the 4 ds_write_b128 are gone), 8 VMEM, 19 -> 14 s_waitcnt.
+// instructions (the 4 ds_write_b128 are gone), 8 VMEM, 19 -> 14 s_waitcnt.  With the pinned schedule, the offsets built
+// once and the shared output stage: VGPRs 196 / 212 / 200 / 212 (the residual instances hold 32 residual + 32 exchanged
+// values across the output stage; the K loop itself needs 196 / 200), same LDS, occupancy 2, no spills, no scratch, no
+// copies of the 128 accumulator registers; a step <false, false> executes 32 MFMA, 24 VALU (16 v_pk_add, 8 v_cndmask),
+// 32 LDS, 8 VMEM, 43 -> 30 scalar instructions; no s_waitcnt in front of the MFMAs of pair 3.
 // On counters over the 480p / 5-object frame (profiles/r07/pmc/): matrix pipe 0.656 -> 0.688 busy, VALU instructions
 // per launch -18.8 %, MFMA instructions and HBM traffic unchanged; bench.py 170.1 -> 175.8 FPS on one box.
 // `make PROBES=1`: DEVA_WINO_ABLATE switches parts of the step off for timing (1 staging stores, 2 activation loads, 4
 // barrier, 8 weight DMA; results are wrong).  On up_8_4 (probe build 677 us): -13 / -54 / -55 / -28 us, all four -104.
-// Output stage: A^T M A is linear in the rows of M, so each half reduces its own rows to a partial 2x2 output in registers,
-// the ph = 1 waves hand theirs over through LDS (64 KB, the weight tiles' space) and the ph = 0 waves add, apply bias /
-// residual / activation and store.  Residual and bias of eight channels are fetched together, up front: a load issued
-// between the stores is waited for in full (`out` may alias `res`, so the compiler keeps every load behind the stores in
-// front of it -- in the first form that was 16 exposed round trips per workgroup, +20 % on a 32-step layer).
+// Output stage, on all eight waves: A^T M A is linear in the rows of M, so each half reduces its own rows to a partial 2x2
+// output in registers.  Half ph keeps the accumulator rows 8 ph .. 8 ph + 7 (eight of a lane's sixteen output channels:
+// [0, 16) and [32, 48) of the block for ph = 0, the others for ph = 1), hands the partials of the other eight rows over
+// through LDS (64 KB, the weight tiles' space, written and read half by each side) and finishes its own: (partial + partial)
+// + bias + residual, activation, store -- bit-identical to the form in which the ph = 0 waves did all sixteen rows and the
+// ph = 1 waves left after the hand-over (the sum of the two partials is commutative).  Residual and bias of a wave's eight
+// channels are fetched together, up front and in front of the hand-over: a load issued between the stores is waited for
+// in full (`out` may alias `res`, so the compiler keeps every load behind the stores in front of it -- in the first form
+// that was 16 exposed round trips per workgroup, +20 % on a 32-step layer); they stay in flight across the hand-over's
+// barrier (raw, lgkmcnt(0) only).  The 32 exchanged partials of a wave are read in one burst behind the barrier (read at
+// the use, every one was a round trip of its own), and the activation code and `out` are held in scalar registers (read
+// through `p`, the compiler of this form fetches them from the kernel arguments again for every row, each fetch a wait).
 // Grid: cout blocks fastest -- the workgroups that share an activation tile run side by side.  Workgroup b runs on XCD b % 8,
 // each with its own L2: as it is, XCD x sees the cout blocks = x (mod 8) of EVERY tile block -- 1/8 of the weights, all the
 // activations.  Right when the weights are the bigger operand (GRU: 100 MB of U against 33 MB); when the activations are
@@ -179,6 +204,14 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
     poff_b0 = (int)(((int64_t)b * p.bs0 + x0) * 4);
     poff_b1 = (int)(((int64_t)b * p.bs1 + x0) * 4);
   }
+  int voff[4], voff1[4];  // the loads' byte offsets from (source - 16 bytes): the current source's, in1's
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    voff1[i] = poff_b1 + 16 + poff[i];
+    voff[i] = p.c0 > 0 ? poff_b0 + 16 + poff[i] : voff1[i];
+  }
+  uintptr_t act_base = reinterpret_cast<uintptr_t>(p.c0 > 0 ? p.in0 : p.in1) - 16;
+  int act_s = 0;
   float pinf = __builtin_inff();
   asm("" : "+v"(pinf));  // (a limit the compiler cannot see through: median(x, 0, +inf) folds to a max WITH the canonicalising max in front)
   const float llim = lcol ? __builtin_inff() : 0.0f, rlim = rcol ? __builtin_inff() : 0.0f;
@@ -205,15 +238,23 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(ru, (__attribute__((address_space(3))) void*)(sA(buf) + (wave * 64 + 512 * i) * 4), 16, aoff,
                                                i * astride, 0, 0);
   };
+  // Activation loads of step s.  The four row offsets of BOTH sources are built once (voff / voff1); the descriptor base
+  // walks through the channels by one scalar addition per step.  The steps arrive in order (0, 1, 2, ... and the last one
+  // repeated at the tail: `act_s` is the step the base points at), so the switch from in0 to in1 is taken exactly once.
   auto load_act = [&](int s) {
     if (WINO_ABL(2)) return;
-    const int c = s * KC;
-    const bool first = c < p.c0;
-    const float* base = (first ? p.in0 + (int64_t)c * HW : p.in1 + (int64_t)(c - p.c0) * HW) - 4;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(base, 0x7fffffff);
-    const int pb = (first ? poff_b0 : poff_b1) + 16;
+    if (s != act_s) {
+      act_s = s;
+      act_base += KC * HW * 4;
+      if (s * KC == p.c0) {
+        act_base = reinterpret_cast<uintptr_t>(p.in1) - 16;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) rb[i] = buf_load4(rx, pb + poff[i], 0);
+        for (int i = 0; i < 4; ++i) voff[i] = voff1[i];
+      }
+    }
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(reinterpret_cast<const void*>(act_base), 0x7fffffff);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rb[i] = buf_load4(rx, voff[i], 0);
   };
   auto stage_act = [&](auto bufc) {  // rb -> ReLU-on-load, B^T d B -> sB(buf)
     const int buf = bufc;
@@ -284,7 +325,8 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
   // activation loads issued after it are younger; they stay in flight across the barrier.
   auto wg_barrier = [&]() {
     if (WINO_ABL(4)) return;
-    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0x0074);  // vmcnt(4) lgkmcnt(0)
+    asm volatile("s_barrier" ::: "memory");
   };
   constexpr std::integral_constant<int, 0> B0{};
   constexpr std::integral_constant<int, 1> B1{};
@@ -310,19 +352,27 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
     };
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
+      SCHED_PIN();
       read_frag(bufc, (g + 1) & 1, g + 1);
+      SCHED_PIN();
       multiply(g & 1, g);
+      SCHED_PIN();
       if (RELU && g == 2 && tile1) stage_tile1();
     }
     if (!RELU && tile1) stage_tile1();
+    SCHED_PIN();
     wg_barrier();
+    SCHED_PIN();
     if (s + 1 < ksteps) read_frag(other, 0, 0);
+    SCHED_PIN();
     if (s + 2 < ksteps) {
       stage_act(bufc);
       load_w(s + 2, bufc);
       load_act(min(s + 3, ksteps - 1));
     }
+    SCHED_PIN();
     multiply(1, 3);
+    SCHED_PIN();
   };
 
   load_act(0);
@@ -344,37 +394,21 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
   // the exchange area below is the weight tiles' space: the wait is unconditional
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-  // ---- output stage.  Rows of M held by this half -> partial t0 = (A^T M)[0], t1 = (A^T M)[1], then the column pass:
-  //   ph = 0: t0 = M0 + M1, t1 = M1;      ph = 1: t0 = M2, t1 = -M2 - M3
+  // ---- output stage, on all eight waves.  Rows of M held by this half -> partial t0 = (A^T M)[0], t1 = (A^T M)[1], then
+  // the column pass:   ph = 0: t0 = M0 + M1, t1 = M1;      ph = 1: t0 = M2, t1 = -M2 - M3
+  // Half ph finishes the accumulator rows 8 ph .. 8 ph + 7 (eight of the lane's sixteen output channels) and hands the
+  // partials of the other eight over to the other half; (partial + partial) + bias + residual as before (the sum of the two
+  // partials is commutative: bit-identical whichever half adds).
   float* xch = sA(0) + (wq * 16 * 4) * 64 + lane;  // [quadrant][r][a * 2 + j][lane]: 64 KB = both weight tiles
   const int n = n0 + wn * 32 + l31;
   const bool n_ok = n < p.n_tiles;
-  if (ph == 1) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float y[2][2];
-      {
-        const float a0 = acc[0][r], a1 = acc[1][r], a2 = acc[2][r], a3 = acc[3][r];
-        y[0][0] = a0 + a1 + a2;
-        y[0][1] = a1 - a2 - a3;
-        const float b0 = -acc[0][r] - acc[4][r], b1 = -acc[1][r] - acc[5][r], b2 = -acc[2][r] - acc[6][r], b3 = -acc[3][r] - acc[7][r];
-        y[1][0] = b0 + b1 + b2;
-        y[1][1] = b1 - b2 - b3;
-      }
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) xch[(r * 4 + a * 2 + j) * 64] = y[a][j];
-    }
-  }
-  __syncthreads();
-  if (ph == 1 || !n_ok) return;
   int64_t o_base;
   int r_off;
   bool row1;  // the tile's second output row exists (odd heights: the last tile row has one)
   {
-    const int b = n / p.tiles_per_img;
-    const int rr = n - b * p.tiles_per_img;
+    const int nn = min(n, p.n_tiles - 1);
+    const int b = nn / p.tiles_per_img;
+    const int rr = nn - b * p.tiles_per_img;
     const int ty = rr / p.tiles_x, tx = rr - ty * p.tiles_x;
     const int64_t pix = (int64_t)(2 * ty) * p.W + 2 * tx;
     o_base = (int64_t)b * p.cout * HW + pix;
@@ -382,17 +416,34 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
     row1 = 2 * ty + 1 < p.H;
   }
   const __amdgpu_buffer_rsrc_t rres = make_rsrc(RES ? p.res : p.out, RES ? 0x7fffffff : 0);
-#pragma unroll
-  for (int rh = 0; rh < 2; ++rh) {  // eight channels at a time: their residual rows are fetched together
-    f32x2 rv[8][2];
-    float bv[8];
+  auto partial = [&](auto phc, int r, float (&y)[2][2]) {
+    if constexpr (decltype(phc)::value == 0) {
+      const float a0 = acc[0][r] + acc[4][r], a1 = acc[1][r] + acc[5][r], a2 = acc[2][r] + acc[6][r], a3 = acc[3][r] + acc[7][r];
+      y[0][0] = a0 + a1 + a2;
+      y[0][1] = a1 - a2 - a3;
+      const float b0 = acc[4][r], b1 = acc[5][r], b2 = acc[6][r], b3 = acc[7][r];
+      y[1][0] = b0 + b1 + b2;
+      y[1][1] = b1 - b2 - b3;
+    } else {
+      const float a0 = acc[0][r], a1 = acc[1][r], a2 = acc[2][r], a3 = acc[3][r];
+      y[0][0] = a0 + a1 + a2;
+      y[0][1] = a1 - a2 - a3;
+      const float b0 = -acc[0][r] - acc[4][r], b1 = -acc[1][r] - acc[5][r], b2 = -acc[2][r] - acc[6][r], b3 = -acc[3][r] - acc[7][r];
+      y[1][0] = b0 + b1 + b2;
+      y[1][1] = b1 - b2 - b3;
+    }
+  };
+  // residual and bias of the half's eight channels, fetched together and before any store (`out` may alias `res`)
+  f32x2 rv[8][2];
+  float bv[8];
+  auto fetch = [&](auto phc) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const int r = rh * 8 + k;
+      const int r = decltype(phc)::value * 8 + k;
       const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
       bv[k] = p.bias ? p.bias[min(m, p.cout - 1)] : 0.0f;
       if (RES) {
-        const int mo = m < p.cout ? r_off + (int)((int64_t)m * HW * 4) : (int)0x80000000;
+        const int mo = (m < p.cout && n_ok) ? r_off + (int)((int64_t)m * HW * 4) : (int)0x80000000;
 #pragma unroll
         for (int a = 0; a < 2; ++a)
           rv[k][a] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rres, (a == 0 || row1) ? mo + a * p.W * 4 : (int)0x80000000, 0, 0));
@@ -400,46 +451,80 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
         rv[k][0] = rv[k][1] = f32x2{0.0f, 0.0f};
       }
     }
-    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto hand_over = [&](auto phc) {  // the other half's rows
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const int r = rh * 8 + k;
+      const int r = (1 - decltype(phc)::value) * 8 + k;
+      float y[2][2];
+      partial(phc, r, y);
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) xch[(r * 4 + a * 2 + j) * 64] = y[a][j];
+    }
+  };
+  // (kept in scalar registers: read through `p` they are fetched again for every row, each fetch a wait)
+  int act = p.act;
+  float* outp = p.out;
+  asm("" : "+s"(act), "+s"(outp));
+  auto finish = [&](auto phc) {
+    float xv[8][4];  // the other half's partials, all 32 reads in flight at once (read at the use, every one is a round trip)
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xv[k][e] = xch[((decltype(phc)::value * 8 + k) * 4 + e) * 64];
+    SCHED_PIN();
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int r = decltype(phc)::value * 8 + k;
       const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
       if (m >= p.cout) continue;
       float y[2][2];
-      {
-        const float a0 = acc[0][r] + acc[4][r], a1 = acc[1][r] + acc[5][r], a2 = acc[2][r] + acc[6][r], a3 = acc[3][r] + acc[7][r];
-        y[0][0] = a0 + a1 + a2;
-        y[0][1] = a1 - a2 - a3;
-        const float b0 = acc[4][r], b1 = acc[5][r], b2 = acc[6][r], b3 = acc[7][r];
-        y[1][0] = b0 + b1 + b2;
-        y[1][1] = b1 - b2 - b3;
-      }
+      partial(phc, r, y);
       const int64_t o = o_base + (int64_t)m * HW;
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
         f32x2 v;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          float x = (y[a][j] + xch[(r * 4 + a * 2 + j) * 64]) + bv[k] + rv[k][a][j];
-          if (p.act == DEVA_ACT_RELU) {
+          float x = (y[a][j] + xv[k][a * 2 + j]) + bv[k] + rv[k][a][j];
+          if (act == DEVA_ACT_RELU) {
             x = fmaxf(x, 0.0f);
-          } else if (p.act == DEVA_ACT_SIGMOID) {
+          } else if (act == DEVA_ACT_SIGMOID) {
             x = sigmoidf_(x);
-          } else if (p.act == DEVA_ACT_SQUARE_PLUS_ONE) {
+          } else if (act == DEVA_ACT_SQUARE_PLUS_ONE) {
             x = x * x + 1.0f;
           }
           v[j] = x;
         }
-        if (a == 0 || row1) *reinterpret_cast<f32x2*>(p.out + o + (int64_t)a * p.W) = v;
+        if (a == 0 || row1) *reinterpret_cast<f32x2*>(outp + o + (int64_t)a * p.W) = v;
       }
     }
-    __builtin_amdgcn_sched_barrier(0);
+  };
+  if (ph == 0) {
+    fetch(B0);
+    SCHED_PIN();
+    hand_over(B0);
+  } else {
+    fetch(B1);
+    SCHED_PIN();
+    hand_over(B1);
+  }
+  // (a raw barrier: the LDS stores are waited for, the residual / bias loads stay in flight across it)
+  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+  asm volatile("s_barrier" ::: "memory");
+  if (!n_ok) return;
+  if (ph == 0) {
+    finish(B0);
+  } else {
+    finish(B1);
   }
 }
 
 #undef sA
 #undef sB
+#undef SCHED_PIN
 
 }  // namespace
 
