@@ -536,6 +536,57 @@ int deva_ensemble_index_mask(const deva_ensemble_variant* variants, int n_varian
  * overlap src. */
 int deva_flip_w(const void* src, void* dst, int64_t rows, int width, int elem_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Per-frame results (deva/inference/result_utils.py:88-285: what ResultSaver / save_result compute on
+ * the host from an int64 mask, one full-frame pass per object and product).
+ *
+ * deva_frame_result: one pass over the [channels][height][width] fp32 probabilities at the output size.
+ *   Per output pixel `best` is the channel index deva_index_mask decides (the same device function:
+ *   same-size fast path, F.interpolate bilinear align_corners=False, first maximum), and
+ *   id = lut ? lut[best] (0 beyond n_lut) : best.  Every output is optional (NULL = not wanted; at
+ *   least one must be given):
+ *     index   int16 [oh][ow]     best (needs channels <= 32767); the plane deva_mask_rle_count reads
+ *     labels  int64 [oh][ow]     id: what deva_index_mask returns
+ *     stats   int32 [channels][5] area, x_min, y_min, x_max, y_max of the pixels of each channel
+ *                                (inclusive pixel coordinates; exact: integer atomics).  Initialised
+ *                                here; a channel without a pixel keeps area 0, minima INT32_MAX and
+ *                                maxima -1.  Tables of up to 1024 channels are accumulated per
+ *                                workgroup in LDS, larger ones with global atomics.
+ *     color   uint8 [oh][ow][3]  color_lut[best] (color_lut: uint8 [channels][3], built by the host: the
+ *                                long-id encoding (id % 256, id / 256 % 256, id / 65536 % 256) of
+ *                                pano_utils.py:23-28 / result_utils.py:208-215, or any palette)
+ *     gray    uint8 [oh][ow]     id & 0xff: the astype(np.uint8) plane of result_utils.py:217
+ *     blend   uint8 [oh][ow][3]  the overlay of result_utils.py:240-242 on image (uint8 [oh][ow][3]):
+ *                                the image byte where id == 0, else (image + color_lut[best]) >> 1 --
+ *                                the float form (image*alpha + rgb*(1-alpha)).astype(uint8), alpha 1 or
+ *                                0.5, is exact in fp32 for bytes and truncates to this
+ *   Rows whose width is a multiple of 4 on suitably aligned planes are stored 4 pixels at a time;
+ *   anything else element by element, with the same bytes.
+ *
+ * deva_mask_rle_count / deva_mask_rle_write: the COCO run boundaries of every object of a frame from
+ *   the index plane.  Positions are column-major, p = x*out_height + y; the label before p = 0 is "no
+ *   object" (as are channel 0 and values outside 1..channels-1).  For every channel c >= 1, bounds_c is
+ *   the ascending list of the p with (index[p] == c) != (index[p-1] == c); the COCO counts of c are
+ *   diff([0, *bounds_c, oh*ow]) (a mask that starts with a 1 gets a leading 0, an absent object gives
+ *   [oh*ow]).  A change from a to b at p is one boundary of a and one of b: 2*oh*ow in all at most.
+ *   count: n[c] = len(bounds_c) (int32 [channels], device; n[0] = 0).
+ *   write: bounds (int32, device) = bounds_1, bounds_2, ... back to back; n_host is the caller's host
+ *   copy of n and `capacity` the number of elements of bounds: refused unless sum(n_host) <= capacity
+ *   (nothing is ever written at or beyond capacity).  write must follow count on the same stream with
+ *   the same, untouched scratch: deva_mask_rle_scratch(oh, ow, channels) bytes of device memory,
+ *   4-byte aligned (it holds the transposed plane and the per-workgroup offsets).  At most 4096
+ *   channels and 2^30 pixels; deva_mask_rle_scratch returns -1 beyond. */
+int deva_frame_result(const float* prob, int channels, int height, int width, int out_height,
+                      int out_width, const int64_t* lut, int n_lut, const uint8_t* color_lut,
+                      const uint8_t* image, int16_t* index, int64_t* labels, int32_t* stats,
+                      uint8_t* color, uint8_t* gray, uint8_t* blend, void* stream);
+int64_t deva_mask_rle_scratch(int out_height, int out_width, int channels);
+int deva_mask_rle_count(const int16_t* index, int out_height, int out_width, int channels,
+                        void* scratch, int64_t scratch_bytes, int32_t* n, void* stream);
+int deva_mask_rle_write(int out_height, int out_width, int channels, const void* scratch,
+                        int64_t scratch_bytes, const int32_t* n_host, int32_t* bounds,
+                        int64_t capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 // exact and order-independent), the host takes all IoU decisions from that small matrix, and one more
 // pass paints the merged result straight into one-hot planes.
 #include "common.h"
+#include "index_argmax.h"
 
 namespace deva {
 namespace {
@@ -90,43 +91,15 @@ __global__ void lut_remap_kernel(const int64_t* __restrict__ in, const int64_t* 
 // align_corners=False) of every channel to (oh, ow) when the size differs, first-maximum argmax, and the
 // tmp-id -> object-id table.  The (no+1)*H*W fp32 probabilities never leave the device; the host
 // copies H*W labels.  Bilinear arithmetic follows ATen's upsample_bilinear2d: source coordinate
-// scale*(dst+0.5)-0.5 clamped at 0, neighbour index clamped at the border, rows blended after columns.
+// scale*(dst+0.5)-0.5 clamped at 0, neighbour index clamped at the border, rows blended after columns
+// (resized_argmax, index_argmax.h: the decision deva_frame_result shares).
 __global__ void index_mask_kernel(const float* __restrict__ prob, int channels, int h, int w, int oh, int ow,
                                   float scale_y, float scale_x, const int64_t* __restrict__ lut, int n_lut,
                                   int64_t* __restrict__ out) {
   const int64_t total = (int64_t)oh * ow;
-  const int64_t plane = (int64_t)h * w;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int y = (int)(i / ow), x = (int)(i - (int64_t)y * ow);
-    int best = 0;
-    if (oh == h && ow == w) {
-      float bv = prob[i];
-      for (int c = 1; c < channels; ++c) {
-        const float v = prob[(int64_t)c * plane + i];
-        if (v > bv) {
-          bv = v;
-          best = c;
-        }
-      }
-    } else {
-      const float sy = fmaxf(scale_y * ((float)y + 0.5f) - 0.5f, 0.0f);
-      const float sx = fmaxf(scale_x * ((float)x + 0.5f) - 0.5f, 0.0f);
-      const int y0 = min((int)sy, h - 1), x0 = min((int)sx, w - 1);
-      const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-      const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
-      const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
-      float bv = -INFINITY;
-      for (int c = 0; c < channels; ++c) {
-        const float* pc = prob + (int64_t)c * plane;
-        const float top = lx0 * pc[(int64_t)y0 * w + x0] + lx1 * pc[(int64_t)y0 * w + x1];
-        const float bot = lx0 * pc[(int64_t)y1 * w + x0] + lx1 * pc[(int64_t)y1 * w + x1];
-        const float v = ly0 * top + ly1 * bot;
-        if (v > bv) {
-          bv = v;
-          best = c;
-        }
-      }
-    }
+    const int best = resized_argmax(prob, channels, h, w, oh, ow, scale_y, scale_x, y, x);
     out[i] = lut ? ((best < n_lut) ? lut[best] : 0) : (int64_t)best;
   }
 }

@@ -132,6 +132,11 @@ SIGNATURES = {
     'deva_ensemble_index_mask': (c_int, [POINTER(EnsembleVariant), c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                          c_void_p]),
     'deva_flip_w': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    'deva_frame_result': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'deva_mask_rle_scratch': (c_int64, [c_int, c_int, c_int]),
+    'deva_mask_rle_count': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    'deva_mask_rle_write': (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _LIB = None

@@ -7,7 +7,7 @@ fallback path.
 """
 from ctypes import c_void_p
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -19,7 +19,7 @@ __all__ = ['PackedConv', 'pack_conv', 'conv2d', 'split_fallbacks', 'PackedStem',
            'affinity_topk', 'BankPrep', 'affinity_dense', 'dense_read', 'affinity_candidates', 'affinity_merge', 'usage_update', 'readout_sparse', 'bank_append', 'bank_gather_rows',
            'bank_export', 'rank', 'rank_select', 'evict_select', 'similarity_dense', 'softmax_columns',
            'label_histogram', 'merge_paint', 'lut_remap', 'index_mask', 'input_head',
-           'scores_u8', 'ensemble_index_mask', 'flip_w',
+           'scores_u8', 'ensemble_index_mask', 'flip_w', 'frame_result', 'mask_rle', 'FrameProducts',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_SQUARE_PLUS_ONE']
 
 
@@ -1039,3 +1039,93 @@ def flip_w(x: torch.Tensor) -> torch.Tensor:
     out = _alloc(x.shape, x.device) if x.dtype == torch.float32 else torch.empty_like(x)
     check(lib().deva_flip_w(x.data_ptr(), out.data_ptr(), rows, width, elem, _stream()), 'deva_flip_w')
     return out
+
+
+# ------------------------------------------------------------------------------------------ per-frame results
+FRAME_PRODUCTS = ('index', 'labels', 'stats', 'color', 'gray', 'blend')
+RLE_MAX_CHANNELS = 4096
+
+
+class FrameProducts(NamedTuple):
+    """device tensors of one `frame_result` call; a product that was not asked for is None"""
+    index: Optional[torch.Tensor] = None    # int16 [OH,OW] channel index
+    labels: Optional[torch.Tensor] = None   # int64 [OH,OW] lut[index]: what `index_mask` returns
+    stats: Optional[torch.Tensor] = None    # int32 [C,5] area, x_min, y_min, x_max, y_max per channel
+    color: Optional[torch.Tensor] = None    # uint8 [OH,OW,3] color_lut[index]
+    gray: Optional[torch.Tensor] = None     # uint8 [OH,OW] lut[index] & 0xff
+    blend: Optional[torch.Tensor] = None    # uint8 [OH,OW,3] image where lut[index] == 0, else (image + color) >> 1
+
+
+def frame_result(prob: torch.Tensor, size: Optional[Tuple[int, int]] = None, lut: Optional[torch.Tensor] = None, *,
+                 color_lut: Optional[torch.Tensor] = None, image: Optional[torch.Tensor] = None,
+                 want=('index', 'labels', 'stats'), out: Optional[dict] = None) -> FrameProducts:
+    """[C,H,W] probabilities -> the per-frame products named in `want`, in one pass at the output size (`size`, or
+    (H,W)): the channel index is the one `index_mask` decides (bilinear resize with align_corners=False when the size
+    differs, first maximum).  `lut` int64 [<=C] maps channels to ids (identity without it), `color_lut` uint8 [C,3]
+    gives the colours of 'color' / 'blend', `image` uint8 [OH,OW,3] is the frame under the 'blend' overlay.  `out` may
+    hold preallocated tensors by product name."""
+    want = tuple(want)
+    if not want or any(w not in FRAME_PRODUCTS for w in want):
+        raise DevaHipError(f'frame_result: want must name some of {FRAME_PRODUCTS} (got {want})')
+    if prob.dim() != 3:
+        raise DevaHipError(f'frame_result: [C,H,W] probabilities expected (got {tuple(prob.shape)})')
+    c, h, w = prob.shape
+    oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if oh <= 0 or ow <= 0:
+        raise DevaHipError(f'frame_result: bad output size {(oh, ow)}')
+    if 'index' in want and c > 32767:
+        raise DevaHipError(f'frame_result: the int16 index plane holds at most 32767 channels (got {c})')
+    if lut is not None and (lut.dim() != 1 or lut.numel() == 0):
+        raise DevaHipError('frame_result: the id table must be a non-empty int64 vector')
+    if ('color' in want or 'blend' in want) and (color_lut is None or tuple(color_lut.shape) != (c, 3)):
+        raise DevaHipError(f'frame_result: color / blend need a uint8 [{c}, 3] color table')
+    if 'blend' in want and (image is None or tuple(image.shape) != (oh, ow, 3)):
+        raise DevaHipError(f'frame_result: blend needs a uint8 image of the output size [{oh}, {ow}, 3] '
+                           f'(got {None if image is None else tuple(image.shape)})')
+    shapes = dict(index=((oh, ow), torch.int16), labels=((oh, ow), torch.int64), stats=((c, 5), torch.int32),
+                  color=((oh, ow, 3), torch.uint8), gray=((oh, ow), torch.uint8), blend=((oh, ow, 3), torch.uint8))
+    res, ptr = {}, {}
+    for name in want:
+        shape, dtype = shapes[name]
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=prob.device)
+        elif tuple(t.shape) != shape:
+            raise DevaHipError(f'frame_result: out[{name!r}] must be {shape} (got {tuple(t.shape)})')
+        res[name], ptr[name] = t, _p(t, dtype, f'out[{name!r}]')
+    n = 0 if lut is None else lut.numel()
+    check(lib().deva_frame_result(_p(prob, name='prob'), c, h, w, oh, ow, _p(lut, torch.int64, 'lut'), n,
+                                  _p(color_lut, torch.uint8, 'color_lut') if ('color' in want or 'blend' in want) else None,
+                                  _p(image, torch.uint8, 'image') if 'blend' in want else None,
+                                  ptr.get('index'), ptr.get('labels'), ptr.get('stats'), ptr.get('color'),
+                                  ptr.get('gray'), ptr.get('blend'), _stream()), 'deva_frame_result')
+    return FrameProducts(**res)
+
+
+def mask_rle(index: torch.Tensor, channels: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """int16 [OH,OW] channel-index plane (`frame_result(...).index`) -> (n, bounds): the COCO run boundaries of every
+    channel c >= 1.  Positions are column-major (p = x*OH + y) and start after "no object"; bounds_c = the ascending p
+    with (index[p] == c) != (index[p-1] == c); n (int32 [channels], on the HOST: reading it is what sizes `bounds`,
+    one synchronisation) holds len(bounds_c) and bounds (int32, device) the lists back to back in channel order.  The
+    COCO counts of c are diff([0, *bounds_c, OH*OW]).  `channels` defaults to index.max() + 1 (another synchronisation);
+    values outside 1..channels-1 count as "no object"."""
+    if index.dim() != 2 or index.dtype != torch.int16:
+        raise DevaHipError(f'mask_rle: an int16 [OH,OW] index plane expected (got {index.dtype} {tuple(index.shape)})')
+    ptr = _p(index, torch.int16, 'index')
+    oh, ow = index.shape
+    c = int(index.max()) + 1 if channels is None else int(channels)
+    if not 1 <= c <= RLE_MAX_CHANNELS:
+        raise DevaHipError(f'mask_rle: 1 to {RLE_MAX_CHANNELS} channels (got {c})')
+    nbytes = lib().deva_mask_rle_scratch(oh, ow, c)
+    if nbytes < 0:
+        raise DevaHipError(f'mask_rle: a frame of {oh} x {ow} with {c} channels is not supported')
+    scratch = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=index.device)
+    n_dev = torch.empty(c, dtype=torch.int32, device=index.device)
+    check(lib().deva_mask_rle_count(ptr, oh, ow, c, scratch.data_ptr(), nbytes, _p(n_dev, torch.int32), _stream()),
+          'deva_mask_rle_count')
+    n = n_dev.cpu()                                        # (synchronises: the exact size of `bounds`)
+    total = int(n.sum())
+    bounds = torch.empty(total, dtype=torch.int32, device=index.device)
+    check(lib().deva_mask_rle_write(oh, ow, c, scratch.data_ptr(), nbytes, n.data_ptr(),
+                                    bounds.data_ptr() if total else None, total, _stream()), 'deva_mask_rle_write')
+    return n, bounds

@@ -137,6 +137,17 @@ class ObjectManager:
         from deva.hip import ops
         return ops.index_mask(prob.contiguous(), size, self._tmp_to_obj_table(prob.device))
 
+    def frame_result(self, prob: torch.Tensor, size=None, *, image=None, rle: bool = False, color=None,
+                     labels: bool = False):
+        """everything a frame's consumer needs from the probabilities of `DEVAInferenceCore.step`, in one device pass
+        (plus the run-length kernels with rle=True) instead of the per-object host passes of the reference's saver
+        (result_utils.py:98-242): a `FrameResult` with the gray or colour id plane, the overlay on `image` and, if
+        asked, the object-id labels of `prob_to_obj_cls` still on the device, and one host-side record per object of
+        `get_current_segments_info()` with area, bbox and (rle=True) the COCO dict (deva/inference/frame_results.py;
+        not part of the reference's interface)"""
+        from deva.inference.frame_results import launch_frame
+        return launch_frame(self, prob, size, image=image, rle=rle, color=color, labels=labels).finish()
+
     def tmp_to_obj_cls(self, mask) -> torch.Tensor:
         """tmp-id index mask -> object-id index mask"""
         if mask.is_cuda and mask.dtype == torch.int64 and self.tmp_id_to_obj:
