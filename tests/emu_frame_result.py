@@ -34,10 +34,9 @@ def products_from_index(index, channels, lut=None, color_lut=None, image=None, w
     if 'stats' in want:
         stats = np.zeros((channels, 5), dtype=np.int32)
         stats[:, 1:3], stats[:, 3:5] = INT_MAX, -1
-        for c in range(channels):
+        for c in np.unique(idx).tolist():   # the channels that are present: an absent one keeps the empty pattern
             ys, xs = np.nonzero(idx == c)
-            if len(ys):
-                stats[c] = (len(ys), xs.min(), ys.min(), xs.max(), ys.max())
+            stats[c] = (len(ys), xs.min(), ys.min(), xs.max(), ys.max())
         out['stats'] = stats
     if 'gray' in want:
         out['gray'] = (ids & 0xff).astype(np.uint8)
@@ -88,8 +87,30 @@ def rle_bounds(index, channels):
     return n, bounds
 
 
+def rle_bounds_fast(index, channels):
+    """`rle_bounds` without the loop over channels, for tables of thousands of them -> (n int32 [channels], the lists
+    back to back, int32): at every position p where the object label of the column-major plane changes (values outside
+    1..channels-1 read as 0, and so does the label before p = 0) the run of `prev` ends and the run of `cur` starts, so
+    (prev, p) and (cur, p) are emitted for the non-zero ones in position order; a stable sort by channel then leaves
+    every channel's positions ascending.  Held equal to `rle_bounds` by tests/test_frame_result_cpu.py."""
+    idx = np.asarray(index.cpu() if torch.is_tensor(index) else index).astype(np.int64)
+    flat = idx.T.reshape(-1)
+    obj = np.where((flat >= 1) & (flat < channels), flat, 0)
+    prev = np.concatenate([[0], obj[:-1]])
+    at = np.nonzero(obj != prev)[0]
+    label = np.stack([prev[at], obj[at]], axis=1).reshape(-1)   # (prev, cur) of each transition, in position order
+    where = np.repeat(at, 2)
+    keep = label != 0
+    label, where = label[keep], where[keep]
+    order = np.argsort(label, kind='stable')
+    return np.bincount(label, minlength=channels).astype(np.int32), where[order].astype(np.int32)
+
+
 def mask_rle(index, channels=None):
     c = int(index.max()) + 1 if channels is None else int(channels)
+    if c > 2048:   # (the loop over channels takes a quarter of a minute at 4096 of them on half a million positions)
+        n, bounds = rle_bounds_fast(index, c)
+        return torch.from_numpy(n), torch.from_numpy(bounds)
     n, bounds = rle_bounds(index, c)
     return torch.from_numpy(n), torch.from_numpy(np.concatenate(bounds).astype(np.int32))
 

@@ -14,6 +14,7 @@ from PIL import Image
 
 import emu_frame_result as E
 import emu_ops
+import full_frame_shapes as FS
 import result_case as RC
 
 torch.set_grad_enabled(False)
@@ -185,6 +186,92 @@ def test_contract_of_the_products():
     alpha = ((ids == 0).astype(np.float32) * 0.5 + 0.5)[:, :, None]
     assert np.array_equal(res.blend.numpy(), (image.numpy() * alpha + rgb * (1 - alpha)).astype(np.uint8))
     assert np.array_equal(res.gray.numpy(), ids.astype(np.uint8))
+
+
+def test_vectorised_boundary_reference_equals_the_loop():
+    """`E.rle_bounds_fast` (what the 4096-channel device test is judged by) against `E.rle_bounds` on every hand-built
+    plane of the device tests and on random planes with values outside the table, of both signs and at both ends"""
+    from test_gpu_o_frame_result import _planes
+    cases = [(plane, channels) for _, plane, channels in _planes(33, 47)]
+    rng = np.random.default_rng(5)
+    for t in range(12):
+        h, w, channels = int(rng.integers(1, 30)), int(rng.integers(1, 30)), int(rng.integers(1, 9))
+        plane = rng.integers(-2, channels + 2, size=(h, w)).astype(np.int16)
+        plane[rng.random((h, w)) < 0.1] = (-32768, 32767, channels, -1)[t % 4]
+        if t % 3 == 0:
+            plane[:, : w // 2] = channels - 1     # long runs (of the background when channels == 1)
+        cases.append((plane, channels))
+    for plane, channels in cases:
+        n, bounds = E.rle_bounds(plane, channels)
+        fast_n, fast_b = E.rle_bounds_fast(plane, channels)
+        assert fast_n.dtype == np.int32 and fast_b.dtype == np.int32
+        assert np.array_equal(fast_n, n) and np.array_equal(fast_b, np.concatenate(bounds))
+
+
+# ------------------------------------------------------------------------------------------ shapes and the paths they reach
+# the caps of the grids, each written once, with the line of the launcher it mirrors
+FRAME_RESULT_BLOCKS = 4096     # csrc/frame_result.hip, deva_frame_result: `if (blocks > 4096) blocks = 4096;`
+LUT_REMAP_BLOCKS = 8192        # csrc/merge.hip, deva_lut_remap: `if (blocks > 8192) blocks = 8192;`
+MERGE_PAINT_BLOCKS = 8192      # csrc/merge.hip, deva_merge_paint: `if (blocks > 8192) blocks = 8192;`
+LABEL_HISTOGRAM_BLOCKS = 2048  # csrc/merge.hip, deva_label_histogram: `if (blocks > 2048) blocks = 2048;`
+THREADS = 256                  # `dim3(256)` in all four launches; frame_result: one 4-pixel group per thread and step
+SCAN_THREADS = 256             # csrc/frame_result.hip, rle_scan_kernel: `const int chunk = (groups + 255) / 256;`
+
+
+def _ceil256(v):
+    return -(-v // 256) * 256
+
+
+def _rle_groups(h, w, channels):
+    """the number of ranges `rle_plan` makes, from the scratch size it asks for: ceil256(2 * total) for the transposed
+    plane, ceil256(4 * channels * groups) for the count table, ceil256(4 * channels) for the bases.  With 64 | channels
+    the middle term is exactly 4 * channels * groups"""
+    from deva import hip
+    assert channels % 64 == 0
+    nbytes = hip.lib().deva_mask_rle_scratch(h, w, channels)
+    middle = nbytes - _ceil256(2 * h * w) - _ceil256(4 * channels)
+    assert middle > 0 and middle % (4 * channels) == 0
+    return middle // (4 * channels)
+
+
+def test_rle_shapes_reach_the_paths_they_are_named_for():
+    """254 ranges for the plane the suite already had (one table entry per scan thread), 282 and 771 for the two new
+    ones (chunks of 2 and 4, the last busy thread of the larger with 3), 945 ranges of more than 512 positions at 4096
+    channels"""
+    for (h, w, groups, chunk) in (FS.RLE_ONE_ENTRY, FS.RLE_TWO_ENTRIES, FS.RLE_PARTIAL_CHUNK):
+        assert _rle_groups(h, w, 64) == groups == -(-h * w // 512)
+        assert -(-groups // SCAN_THREADS) == chunk
+    assert [s[2] for s in (FS.RLE_ONE_ENTRY, FS.RLE_TWO_ENTRIES, FS.RLE_PARTIAL_CHUNK, FS.RLE_GROWN_RANGE)] == \
+        [254, 282, 771, 945]
+    groups = FS.RLE_TWO_ENTRIES[2]
+    assert groups % 2 == 0 and groups // 2 == 141                       # threads 0..140 busy, no partial chunk
+    groups = FS.RLE_PARTIAL_CHUNK[2]
+    assert groups // 4 == 192 and groups % 4 == 3 and SCAN_THREADS - 193 == 63
+    h, w, groups, chunk = FS.RLE_GROWN_RANGE
+    assert _rle_groups(h, w, FS.RLE_GROWN_CHANNELS) == groups and -(-groups // SCAN_THREADS) == chunk
+    assert groups < -(-h * w // 512)                                      # the range really grew ...
+    assert -(-h * w // groups) > 512 and -(-h * w // 576) == groups       # ... to 576 positions
+    assert 4 * FS.RLE_GROWN_CHANNELS * groups > 15 * 10**6                # the count table: 15.5 MB
+
+
+def test_full_frame_shapes_exceed_the_grid_caps():
+    (oh, ow), (eh, ew) = FS.FRAME_PACKED, FS.FRAME_ELEMENTWISE
+    assert ow % 4 == 0 and oh * (ow // 4) == 1050624 > FRAME_RESULT_BLOCKS * THREADS
+    assert ew % 4 == 2 and eh * ((ew + 3) // 4) == 1052676 > FRAME_RESULT_BLOCKS * THREADS
+    pixels = FS.MERGE_LARGE[0] * FS.MERGE_LARGE[1]
+    assert pixels > LUT_REMAP_BLOCKS * THREADS and pixels > MERGE_PAINT_BLOCKS * THREADS
+    assert pixels > LABEL_HISTOGRAM_BLOCKS * THREADS
+    assert 1080 * 1920 <= LUT_REMAP_BLOCKS * THREADS                      # (what 1080p does not reach)
+    # the mirrored lines are still what the launchers say
+    csrc = os.path.join(ROOT, 'tracking-anything-with-deva_amd', 'csrc')
+    bodies = {}
+    for file in ('frame_result.hip', 'merge.hip'):
+        for part in open(os.path.join(csrc, file)).read().split('extern "C" ')[1:]:
+            bodies[re.match(r'\w+ (\w+)', part).group(1)] = part
+    for name, cap in (('deva_frame_result', FRAME_RESULT_BLOCKS), ('deva_lut_remap', LUT_REMAP_BLOCKS),
+                      ('deva_merge_paint', MERGE_PAINT_BLOCKS), ('deva_label_histogram', LABEL_HISTOGRAM_BLOCKS)):
+        assert f'if (blocks > {cap}) blocks = {cap};' in bodies[name], name
+        assert f'dim3({THREADS})' in bodies[name] or f't({THREADS})' in bodies[name], name
 
 
 # ------------------------------------------------------------------------------------------ saver against the reference's

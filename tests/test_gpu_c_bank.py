@@ -3,6 +3,7 @@ import pytest
 import torch
 
 import emu_ops
+import full_frame_shapes as FS
 from deva.hip import ops
 from gpu_util import dev, max_err, rand, to_dev
 
@@ -92,6 +93,18 @@ def test_similarity_dense_and_softmax_columns(nc, p):
 @pytest.mark.parametrize('h,w,n_our,n_new', [(64, 80, 3, 4), (480, 864, 8, 12), (17, 5, 0, 2), (33, 47, 5, 0),
                                              (240, 320, 150, 140)])
 def test_label_histogram_and_merge_paint(h, w, n_our, n_new):
+    _histogram_and_paint(h, w, n_our, n_new, n_out=6)
+
+
+def test_label_histogram_and_merge_paint_beyond_the_grid_caps():
+    """1025 x 2049 = 2 100 225 pixels with small tables: more pixels than the 8192 x 256 threads `merge_paint` is
+    capped at (a 1080p frame fits under the cap exactly, a 4K frame does not), and five steps of the histogram's
+    2048 x 256"""
+    got = _histogram_and_paint(*FS.MERGE_LARGE, n_our=3, n_new=4, n_out=3)
+    assert got.shape == (3, *FS.MERGE_LARGE) and 0 < float(got.sum()) <= got[0].numel()
+
+
+def _histogram_and_paint(h, w, n_our, n_new, n_out):
     g = torch.Generator().manual_seed(h + n_our)
     ours = torch.randint(0, n_our + 1, (h, w), generator=g)
     new_ids = (torch.randperm(5000, generator=g)[:n_new] + 300).long()
@@ -106,11 +119,12 @@ def test_label_histogram_and_merge_paint(h, w, n_our, n_new):
     our_label = torch.randint(1, 400, (n_our + 1,), generator=g)
     new_order = torch.randint(-1, 6, (n_new,), generator=g).int()
     new_label = torch.randint(1, 400, (n_new,), generator=g)
-    out_ids = torch.unique(torch.cat([our_label, new_label]))[:6]
+    out_ids = torch.unique(torch.cat([our_label, new_label]))[:n_out]
     want = emu_ops.merge_paint(ours, news, new_ids, our_order, our_label, new_order, new_label, out_ids)
     got = ops.merge_paint(to_dev(ours), to_dev(news), to_dev(new_ids), to_dev(our_order), to_dev(our_label),
                           to_dev(new_order), to_dev(new_label), to_dev(out_ids))
     assert got.shape == want.shape and torch.equal(got.cpu(), want)
+    return got
 
 
 def test_lut_remap_and_tmp_to_obj_cls():
@@ -123,6 +137,27 @@ def test_lut_remap_and_tmp_to_obj_cls():
     got = om.tmp_to_obj_cls(to_dev(mask))        # device path (deva_lut_remap)
     assert torch.equal(got.cpu(), want)
     assert set(want.unique().tolist()) <= {0, 7, 3, 250}
+
+
+@pytest.mark.parametrize('shape', [(37, 53), FS.MERGE_LARGE])
+def test_lut_remap_outside_the_table_and_beyond_the_grid_cap(shape):
+    """`ops.lut_remap` itself: a seventh of the pixels hold -5, n, n + 1 or 2^40 and must come out 0, the others the
+    table's entry; at 1025 x 2049 the 2 100 225 pixels outnumber the 8192 x 256 threads of the capped grid, and the
+    pixels of the second step hold values of every kind"""
+    g = torch.Generator().manual_seed(shape[0])
+    lut = torch.tensor([9, 7, 3, 250, 70000, 2**33 + 5, 1, 2**62, 12], dtype=torch.int64)   # no entry is 0
+    n = lut.numel()
+    mask = torch.randint(0, n, shape, generator=g)
+    flat = mask.view(-1)
+    at = torch.randperm(flat.numel(), generator=g)[:flat.numel() // 7]
+    flat[at] = torch.tensor([-5, n, n + 1, 2**40])[torch.arange(at.numel()) % 4]
+    flat[-8:] = torch.tensor([-5, 0, n, n - 1, n + 1, 4, 2**40, 2])
+    got = ops.lut_remap(to_dev(mask), to_dev(lut)).cpu()
+    assert got.dtype == torch.int64 and got.shape == mask.shape and torch.equal(got, emu_ops.lut_remap(mask, lut))
+    outside = (mask < 0) | (mask >= n)
+    assert all(int((mask == v).sum()) >= 5 for v in (-5, n, n + 1, 2**40))
+    assert int(got[outside].abs().sum()) == 0 and torch.equal(got[~outside], lut[mask[~outside]])
+    assert bool((got[~outside] != 0).all())
 
 
 @pytest.mark.parametrize('c,h,w,size', [(3, 40, 56, None), (6, 480, 864, (1080, 1920)), (2, 33, 47, (97, 61)),

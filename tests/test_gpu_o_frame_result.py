@@ -12,6 +12,7 @@ import torch
 from PIL import Image
 
 import emu_frame_result as E
+import full_frame_shapes as FS
 import gpu_util
 from deva.hip import DevaHipError, check, lib, ops
 from gpu_util import to_dev
@@ -84,6 +85,73 @@ def test_labels_equal_index_mask_and_products_follow_the_index(c, h, w, size):
     assert torch.equal(plain.stats, res.stats)
 
 
+@pytest.mark.parametrize('size', [FS.FRAME_PACKED, FS.FRAME_ELEMENTWISE])
+def test_grid_stride_takes_a_second_step(size):
+    """more 4-pixel groups than the 4096 x 256 threads of the capped grid: the grid-stride loop takes a second step
+    with the LDS statistics table carried across it.  (2052, 2048): the packed stores, 1 050 624 groups; (2052, 2050):
+    the element-wise stores, 513 groups per row with a 2-pixel last one, 1 052 676 groups"""
+    c, h, w = FS.FRAME_PROB
+    prob, lut, colors, image = _inputs(c, h, w, size)
+    dprob, dlut = to_dev(prob), to_dev(lut)
+    res = ops.frame_result(dprob, size, dlut, color_lut=to_dev(colors), image=to_dev(image), want=ALL)
+    assert res.labels.dtype == torch.int64 and torch.equal(res.labels, ops.index_mask(dprob, size, dlut))
+    assert res.index.dtype == torch.int16 and torch.equal(res.index.long(), ops.index_mask(dprob, size))
+    _check_products(res, c, lut, colors, image)
+    assert int(res.stats[:, 0].sum()) == size[0] * size[1]
+    assert res.stats[:, 3].max() == size[1] - 1 and res.stats[:, 4].max() == size[0] - 1
+
+
+@pytest.mark.parametrize('size', [(37, 45), (40, 48)])
+def test_id_table_shorter_than_the_channels(size):
+    """6 channels, ids for the first 4 only: where channel 4 or 5 wins the id is 0 (labels and gray 0, the overlay
+    shows the image), the colour plane still carries the channel's colour and the statistics still count it"""
+    c = 6
+    prob, lut, _, image = _inputs(c, 20, 28, size)
+    lut = lut[:4]
+    colors = torch.tensor([[0, 0, 0], [10, 20, 30], [40, 50, 60], [70, 80, 90], [101, 111, 121], [131, 141, 151]],
+                          dtype=torch.uint8)
+    res = ops.frame_result(to_dev(prob), size, to_dev(lut), color_lut=to_dev(colors), image=to_dev(image), want=ALL)
+    assert torch.equal(res.labels, ops.index_mask(to_dev(prob), size, to_dev(lut)))
+    _check_products(res, c, lut, colors, image)
+    index = res.index.cpu().long()
+    for ch in (4, 5):
+        won = index == ch
+        assert int(won.sum()) > 0
+        assert int(res.labels.cpu()[won].abs().sum()) == 0 and int(res.gray.cpu()[won].sum()) == 0
+        assert torch.equal(res.blend.cpu()[won], image[won])
+        assert bool((res.color.cpu()[won] == colors[ch]).all())
+        ys, xs = torch.nonzero(won, as_tuple=True)
+        assert res.stats[ch].tolist() == [int(won.sum()), int(xs.min()), int(ys.min()), int(xs.max()), int(ys.max())]
+
+
+def test_more_channels_than_the_index_plane_holds():
+    """40 000 channels without the int16 `index` plane: winners at 0, 32767, 32768 and 39999; labels are
+    `index_mask`'s, the statistics the contract's (the absent rows against the empty pattern directly), and asking
+    for `index` is refused"""
+    c, h, w = 40000, 4, 5
+    present = torch.tensor([0, 32767, 32768, 39999])
+    owner = present[(torch.arange(h * w) * 7 % 20 % 4)].view(h, w)
+    prob = torch.full((c, h, w), 0.1 / c)
+    prob.scatter_(0, owner[None], 0.9)
+    lut = torch.arange(c, dtype=torch.int64) * 3 + 1
+    dprob, dlut = to_dev(prob), to_dev(lut)
+    res = ops.frame_result(dprob, None, dlut, want=('labels', 'stats'))
+    assert res.index is None and torch.equal(res.labels, ops.index_mask(dprob, None, dlut))
+    assert torch.equal(res.labels.cpu(), owner * 3 + 1)
+    made = E.products_from_index(owner, c, lut, want=('labels', 'stats'))
+    stats = res.stats.cpu().numpy()
+    assert stats.dtype == np.int32 and stats.shape == (c, 5)
+    for ch in present.tolist():
+        ys, xs = torch.nonzero(owner == ch, as_tuple=True)
+        assert stats[ch].tolist() == [len(ys), int(xs.min()), int(ys.min()), int(xs.max()), int(ys.max())] and len(ys) == 5
+    absent = np.ones(c, dtype=bool)
+    absent[present.numpy()] = False
+    assert np.array_equal(stats[absent], np.tile(np.array([0, E.INT_MAX, E.INT_MAX, -1, -1], dtype=np.int32), (c - 4, 1)))
+    assert np.array_equal(stats, made['stats'])
+    with pytest.raises(DevaHipError):
+        ops.frame_result(dprob, None, dlut, want=('index', 'stats'))
+
+
 def _poisoned(nbytes, offset, guard=64):
     buf = torch.full((guard + offset + nbytes + guard + 16,), 0xA5, dtype=torch.uint8)
     return to_dev(buf), guard + offset
@@ -121,8 +189,9 @@ def test_shifted_outputs_give_the_same_bytes_and_keep_their_guard_bands(c, h, w,
 def test_many_channels_and_the_global_table():
     """300 channels at 24 x 40, every channel present (an 8-bit index or a statistics table sized for few objects
     fails here), and 1100 channels at 24 x 48: beyond the 1024 channels of the LDS table the statistics go through
-    global atomics and must be the same numbers"""
-    for c, h, w in ((300, 24, 40), (1100, 24, 48)):
+    global atomics and must be the same numbers.  The edge itself: 1024 channels at 32 x 32 (the LDS table at its
+    limit, every channel owning one pixel) and 1025 at 25 x 41 (the first global table, on an odd width)"""
+    for c, h, w in ((300, 24, 40), (1100, 24, 48), (1024, 32, 32), (1025, 25, 41)):
         owner = torch.arange(h * w).view(h, w) % c
         prob = torch.full((c, h, w), 0.1 / c)
         prob.scatter_(0, owner[None], 0.9)
@@ -138,17 +207,23 @@ def test_many_channels_and_the_global_table():
 
 
 # ------------------------------------------------------------------------------------------ run boundaries
-def _check_rle(index, channels, n, bounds, strings=True):
+def _check_rle(index, channels, n, bounds, strings=True, fast=False):
+    """`strings`: True decodes every channel's COCO string, a list only those channels (the decoder is a Python loop);
+    `fast`: the vectorised reference, for tables of thousands of channels"""
     from deva.inference.frame_results import rle_strings
-    want_n, want_b = E.rle_bounds(index, channels)
+    if fast:
+        want_n, want_b = E.rle_bounds_fast(index, channels)
+    else:
+        want_n, want_b = E.rle_bounds(index, channels)
+        want_b = np.concatenate(want_b)
     n, bounds = n.cpu().numpy(), bounds.cpu().numpy()
     assert n.dtype == np.int32 and bounds.dtype == np.int32
     assert np.array_equal(n, want_n), (n[:8], want_n[:8])
-    assert np.array_equal(bounds, np.concatenate(want_b))
+    assert np.array_equal(bounds, want_b), f'{int((bounds != want_b).sum())} of {bounds.size} boundaries differ'
     if strings:
         h, w = index.shape
         texts = rle_strings(n, bounds, h * w)
-        for c in range(1, channels):
+        for c in (range(1, channels) if strings is True else strings):
             got = E.coco_decode({'size': [h, w], 'counts': texts[c]})
             assert np.array_equal(got, index.numpy() == c), c
 
@@ -187,6 +262,94 @@ def test_run_boundaries_of_hand_built_planes(h, w):
     # the default channel count is max + 1
     n, _ = ops.mask_rle(to_dev(_planes(h, w)[0][1]))
     assert n.numel() == 5
+
+
+@pytest.mark.parametrize('k', range(8))
+@pytest.mark.parametrize('h,w', [FS.RLE_TWO_ENTRIES[:2], FS.RLE_PARTIAL_CHUNK[:2]])
+def test_run_boundaries_with_several_table_entries_per_thread(h, w, k):
+    """the hand-built planes at 300 x 480 (282 ranges: two table entries per scan thread, 115 idle threads) and at
+    526 x 750 (771 ranges: four entries, thread 192 with a partial chunk of three, 63 idle threads); one case per
+    plane.  The run crossing every boundary leaves ranges without a boundary between ranges that have one; the
+    checkerboard has one at every position, so any wrong prefix offset moves a checked boundary"""
+    planes = _planes(h, w)
+    assert len(planes) == 8
+    name, plane, channels = planes[k]
+    n, bounds = ops.mask_rle(to_dev(plane), channels)
+    _check_rle(plane, channels, n, bounds)
+    if 'checkerboard' in name:
+        assert int(n.sum()) == 2 * h * w - 1, name
+    if 'crossing' in name:
+        assert n.tolist() == [0, 0, 0, 2] and bounds.tolist() == [h, (w - 1) * h]
+
+
+def _scan_order(h, w):
+    yy, xx = torch.meshgrid(torch.arange(h), torch.arange(w), indexing='ij')
+    return xx * h + yy
+
+
+def test_run_boundaries_of_a_full_table_on_a_grown_range():
+    """544 x 1000 with 4096 channels: 945 ranges of 576 positions instead of 512, four table entries per scan thread,
+    4096 scan workgroups.  The label changes every 131 positions of the scan order (131 is prime to 64 and to 576: run
+    ends fall on every lane and cross range ends); the 4153 runs wrap past 4096, so every channel is present and
+    1..56 twice (the second run of 56 reaches the end of the plane: three boundaries, not four)"""
+    h, w = FS.RLE_GROWN_RANGE[:2]
+    channels = FS.RLE_GROWN_CHANNELS
+    plane = ((_scan_order(h, w) // 131) % channels).to(torch.int16)
+    n, bounds = ops.mask_rle(to_dev(plane), channels)
+    _check_rle(plane, channels, n, bounds, strings=[1, 30, 56, 57, 4095], fast=True)
+    assert n[0] == 0 and n[1:56].tolist() == [4] * 55 and n[56] == 3 and n[57:].tolist() == [2] * (channels - 57)
+    p = torch.zeros(h, w, dtype=torch.int16)
+    p[:, 1:w - 1] = channels - 1
+    n, bounds = ops.mask_rle(to_dev(p), channels)
+    _check_rle(p, channels, n, bounds, strings=[1, channels - 1], fast=True)
+    assert int(n.sum()) == 2 and bounds.tolist() == [h, (w - 1) * h]
+
+
+def test_values_outside_the_table_are_no_object():
+    """-1, -32768, `channels` and 32767 in the plane, next to objects, to the background and to each other: the result
+    is that of the plane with those values replaced by 0"""
+    h, w, channels = 19, 23, 5
+    g = torch.Generator().manual_seed(7)
+    clean = torch.randint(0, channels, (h, w), generator=g).to(torch.int16)
+    clean[:, 5:9] = 0
+    hit = torch.rand(h, w, generator=g) < 0.3
+    hit[:4, :] = True      # (a block of nothing but out-of-table values of all four kinds)
+    outside = torch.tensor([-1, -32768, channels, 32767], dtype=torch.int16)[torch.randint(0, 4, (h, w), generator=g)]
+    bad = torch.where(hit, outside, clean)
+    clean = torch.where(hit, torch.zeros_like(clean), clean)
+    assert all(bool((bad == v).any()) for v in outside.unique().tolist())
+    n, bounds = ops.mask_rle(to_dev(bad), channels)
+    n0, bounds0 = ops.mask_rle(to_dev(clean), channels)
+    assert torch.equal(n, n0) and torch.equal(bounds, bounds0) and int(n.sum()) > 100
+    _check_rle(clean, channels, n, bounds)
+    _check_rle(bad, channels, n, bounds, strings=False)
+
+
+@pytest.mark.parametrize('h,w', [(1, 700), (700, 1), (1, 1)])
+def test_run_boundaries_of_planes_one_pixel_high_or_wide(h, w):
+    g = torch.Generator().manual_seed(h + 2 * w)
+    plane = torch.randint(0, 4, (h, w), generator=g).to(torch.int16)
+    plane.view(-1)[0], plane.view(-1)[-1] = 2, 2     # (the first and the last position belong to an object)
+    n, bounds = ops.mask_rle(to_dev(plane), 4)
+    _check_rle(plane, 4, n, bounds)
+    if h * w == 1:
+        assert n.tolist() == [0, 0, 1, 0] and bounds.tolist() == [0]
+        n, bounds = ops.mask_rle(to_dev(torch.zeros(1, 1, dtype=torch.int16)), 4)
+        assert n.tolist() == [0, 0, 0, 0] and bounds.numel() == 0
+
+
+def test_a_table_of_the_background_alone_and_a_full_table():
+    """`channels == 1`: nothing can be an object, n == [0] and no boundaries, without an error; `channels == 4096`, the
+    most the LDS cursors hold, is accepted (test_rle_refusals holds the refusal of 4097)"""
+    plane = (torch.arange(24 * 48).view(24, 48) % 7).to(torch.int16)
+    n, bounds = ops.mask_rle(to_dev(plane), 1)
+    assert n.dtype == torch.int32 and n.tolist() == [0]
+    assert bounds.dtype == torch.int32 and bounds.numel() == 0
+    plane = (torch.arange(24 * 48).view(24, 48) * 5 % 1153).to(torch.int16)    # 1152 distinct labels 0..1152
+    plane[3, 7:11] = 4095
+    n, bounds = ops.mask_rle(to_dev(plane), 4096)
+    _check_rle(plane, 4096, n, bounds, strings=[1, 5, 1152, 4094, 4095])
+    assert n.numel() == 4096 and n[4095] == 8 and n[4094] == 0
 
 
 def test_rle_refusals():
