@@ -147,6 +147,65 @@ typedef struct deva_conv_desc {
  * summation order).  Only a SINGLE image whose source reaches 2^29 floats is refused (error: "one image of a source
  * spans 2 GiB or more"), as is an output of 2^31 pixels or more. */
 int deva_conv2d(const deva_conv_desc* desc, void* stream);
+
+/* What deva_conv2d would launch for a descriptor: kernel family, tile, K split and grid (csrc/conv_plan.cpp; deva_conv2d
+ * obtains its own plan through the same function).  HOST ONLY: no HIP call, no device needed, nothing dereferenced but
+ * the descriptor -- pointer VALUES are used for null-ness, 16-byte alignment (out, residual) and overlap (out against
+ * in0 / in1 / residual under amp == 2) only, so a caller without a device may pass made-up addresses.  Returns what
+ * deva_conv2d returns for a descriptor it refuses before any launch (text via deva_hip_last_error()); `*plan` is then
+ * all zero (family DEVA_CONV_NONE), never partly written. */
+enum {
+  DEVA_CONV_NONE = 0,        /* no launch (deva_conv_plan.rerun of a call that is not a hi/lo split) */
+  DEVA_CONV_COUT1_TABLE = 1, /* single output channel, a dot product per pixel (csrc/conv_cout1.hip) */
+  DEVA_CONV_COUT1_ROWS = 2,  /* single output channel, row-reusing 3x3 on large guard-banded maps */
+  DEVA_CONV_WINO = 3,        /* fp32 Winograd F(2x2, 3x3) (csrc/conv_wino.hip) */
+  DEVA_CONV_F16 = 4,         /* fp16 operands, amp == 1 (csrc/conv_f16.hip) */
+  DEVA_CONV_SPLIT = 5,       /* hi/lo fp16 split, amp == 2 (csrc/conv_f16.hip) */
+  DEVA_CONV_Q4 = 6,          /* fp32 MFMA on k-quad interleaved weights (csrc/conv_mfma.hip) */
+  DEVA_CONV_IGEMM = 7        /* fp32 MFMA on plain [K][cout_pad] weights (csrc/conv_igemm.hip) */
+};
+/* staging kinds (deva_conv_launch.kind) of the MFMA families; F16 / SPLIT use the first two */
+enum {
+  DEVA_CONV_KIND_1X1 = 0,     /* 1x1, 4-pixel vector gathers */
+  DEVA_CONV_KIND_ROWS = 1,    /* 3x3 / pad 1 on 32-channel slabs: an input row staged once serves the three dx taps */
+  DEVA_CONV_KIND_UNIFORM = 2, /* tap and source uniform per K step, scalar gathers */
+  DEVA_CONV_KIND_GENERIC = 3  /* per-element decode (stems, odd channel splits) */
+};
+/* DEVA_CONV_IGEMM: kind = addressing mode (0: 1x1, 1: tap and source uniform per K step, 2: per-element decode), ORed with */
+enum {
+  DEVA_CONV_IGEMM_VEC = 4, /* 4-pixel vector gathers */
+  DEVA_CONV_IGEMM_ROW = 8  /* row reuse (implies VEC) */
+};
+typedef struct deva_conv_launch {
+  int32_t family;      /* DEVA_CONV_* */
+  int32_t bm, bn;      /* workgroup tile: output channels x pixels (WINO: x 2x2 output tiles); 0 for the cout == 1 families */
+  int32_t waves;       /* waves of one K-slice group; the workgroup has waves * wk of them */
+  int32_t wk;          /* K-slice groups per workgroup (1 outside DEVA_CONV_Q4) */
+  int32_t kind;        /* the variant of the family's kernel; its meaning depends on `family`:
+                            Q4, F16, SPLIT: DEVA_CONV_KIND_* (F16 / SPLIT: 1X1 or ROWS)
+                            IGEMM:          addressing mode 0 / 1 / 2, ORed with DEVA_CONV_IGEMM_VEC / _ROW
+                            COUT1_TABLE:    0 / 1 / 2 = pixels x k-groups of a workgroup 64x4, 16x16, 8x32
+                            COUT1_ROWS:     0 = two output rows per strip, 1 = one
+                            WINO:           1 = workgroups renumbered so that an XCD takes a contiguous range of tile blocks */
+  int32_t persistent;  /* the gated fp32 re-run as a persistent kernel: grid_x workgroups loop over tiles_m * tiles_n tiles */
+  int32_t tiles_m, tiles_n;
+  int32_t splits;      /* split-K factor (grid_y); > 1: partial sums go to the first splits * cout * n_total floats of
+                          the workspace and a reduction launch (not listed) follows */
+  int32_t per_split;   /* K steps per split; all of them when splits == 1 */
+  int32_t group_m;     /* cout tiles per tile-order group; 0 = all */
+  uint32_t grid_x, grid_y, block;
+} deva_conv_launch;
+typedef struct deva_conv_plan {
+  deva_conv_launch first;
+  /* DEVA_CONV_SPLIT only: the fp32 launch behind it, gated on split_flag (rerun.persistent, or the regular kernels) */
+  deva_conv_launch rerun;
+  int32_t aliased;   /* amp == 2 and `out` overlaps an operand: the fp32 kernels alone (first is the fp32 launch) */
+  /* images per launch: batch, or fewer when a source spans 2^29 floats (SIZE LIMITS above).  The plan describes the launch
+   * of the first min(sub_batch, batch) images; a shorter tail is planned like a call of its own with that batch. */
+  int32_t sub_batch;
+} deva_conv_plan;
+int deva_conv2d_plan(const deva_conv_desc* desc, deva_conv_plan* plan);
+
 /* fp16 weights of the amp path (HOST pointers, model load): -> number of uint16 elements (out == NULL: size query),
  * -1 when the layer is not eligible (cin % 64 != 0) or on bad arguments */
 int64_t deva_conv_pack_f16(const float* w_oihw, uint16_t* out, int cout, int cin, int kh, int kw, int* cout_pad);

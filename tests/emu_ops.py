@@ -14,6 +14,7 @@ from deva.hip.ops import PackedConv
 
 TWO40 = float(2**40)
 _real_pack_conv = real.pack_conv
+_real_conv_plan = real.conv_plan
 
 
 def require_hip(device, what):  # the emulation runs on the CPU
@@ -46,68 +47,48 @@ def _act(y, act):
     return y
 
 
-def amp_takes(pc, x0, x1, stride, pad):
-    """the shapes csrc/conv_f16.hip takes (launch_conv_f16 + the vector-gather geometry of deva_conv2d); everything
-    else runs fp32 even under amp"""
-    c0, c1 = x0.shape[1], 0 if x1 is None else x1.shape[1]
-    h, w = x0.shape[-2:]
-    return (pc.weight_f16 is not None and stride == 1 and pc.cout >= 64 and c0 % 64 == 0 and c1 % 64 == 0 and
-            ((pc.kh == 1 and pad == 0) or (pc.kh == 3 and pad == 1)) and (h * w) % 4 == 0 and w >= 4 and _guard_ok(w, pad))
-
-
-def _guard_ok(w, pad):
-    """the vector gathers need pad * (W + 1) + 4 readable floats around both inputs (deva_conv2d: vec_ok); the tensors of
-    ops._alloc and of the tests' guarded buffers carry ops.GUARD"""
-    return pad * (w + 1) + 4 <= real.GUARD
-
-
-def split_takes(pc, x0, x1, stride, pad):
-    """the shapes the hi/lo split kernels take (csrc/conv_f16.hip: launch_conv_f16 with prec 2 + the vector-gather
-    geometry of deva_conv2d); everything else runs the fp32 kernels although split is requested"""
-    c0, c1 = x0.shape[1], 0 if x1 is None else x1.shape[1]
-    h, w = x0.shape[-2:]
-    whole = c0 % 32 == 0 and c1 % 32 == 0
-    tail = pc.kh == 1 and (c0 % 32 == 0 if c1 else True)  # 1x1: a partial last K step (513 = 512 + 1 channels) is taken too
-    return (pc.weight_split is not None and stride == 1 and pc.cout >= 64 and (whole or tail) and
-            ((pc.kh == 1 and pad == 0) or (pc.kh == 3 and pad == 1)) and (h * w) % 4 == 0 and w >= 4 and _guard_ok(w, pad))
-
-
-def wino_takes(pc, x0, x1, stride, pad, batch=None):
-    """the shapes the fp32 Winograd kernel takes (csrc/conv_wino.hip: launch_conv_wino + the vector-gather geometry of
-    deva_conv2d), for a call WITHOUT amp / split on guard-banded inputs: 3x3 / stride 1 / pad 1, even width >= 4, a pixel
-    count of 4k, channel counts that are multiples of 8, cout >= 32 and at least 160 workgroups of 64 channels x 64 tiles
-    of 2x2 outputs (odd heights end in a tile row of one output row); rows of at most ops.GUARD - 5 pixels.  batch: of the call (default: the operands')"""
+def plan_of(pc, x0, x1, stride, pad, *, batch=None, amp=False, split=False):
+    """the library's plan (ops.conv_plan -> deva_conv2d_plan, the function deva_conv2d plans with) for the call
+    `ops.conv2d(pc, x0, x1, ...)` issues on tensors of ops._alloc / the tests' guarded buffers (ops.GUARD floats around them).
+    pc: anything with cout, kh, kw and the optional weight sets; batch: of the call (default: the operands')"""
     c0, c1 = x0.shape[1], 0 if x1 is None else x1.shape[1]
     h, w = x0.shape[-2:]
     if batch is None:
         batch = max(x0.shape[0], 1 if x1 is None else x1.shape[0])
-    if not (pc.weight_wino is not None and pc.kh == 3 and pc.kw == 3 and stride == 1 and pad == 1 and pc.cout >= 32):
-        return False
-    if w % 2 or w < 4 or (h * w) % 4 or c0 % 8 or c1 % 8 or not _guard_ok(w, pad):
-        return False
-    tiles = batch * ((h + 1) // 2) * (w // 2)
-    return ((pc.cout + 63) // 64) * ((tiles + 63) // 64) >= 160
+    weights = tuple(n for n, attr in (('f16', 'weight_f16'), ('split', 'weight_split'), ('wino', 'weight_wino'))
+                    if getattr(pc, attr, None) is not None)
+    return _real_conv_plan(c0, c1, pc.cout, pc.kh, pc.kw, stride=stride, pad=pad, batch=batch, height=h, width=w,
+                           k_layout=getattr(pc, 'k_layout', None), weights=weights, amp=amp, split=split,
+                           in0_batch_stride=0 if (x0.shape[0] == 1 and batch > 1) else None,
+                           in1_batch_stride=0 if (x1 is not None and x1.shape[0] == 1 and batch > 1) else None)
 
 
-CONV_SPAN_LIMIT = 1 << 29  # floats one launch of deva_conv2d addresses inside a source (32-bit byte offsets)
+def amp_takes(pc, x0, x1, stride, pad):
+    """does a call with amp run on the fp16-operand kernels (csrc/conv_f16.hip)?  Everything else runs fp32 even under amp"""
+    return plan_of(pc, x0, x1, stride, pad, amp=True).family == 'f16'
 
 
-def conv_sub_batches(batch, c0, hw, stride0, c1=0, stride1=0):
-    """the sub-batches deva_conv2d runs a call as (csrc/conv_igemm.hip, the block in front of ConvArgs): a source spans
-    (batch - 1) * batch_stride + channels * H * W floats; a batch that reaches CONV_SPAN_LIMIT is cut into runs of the
-    largest image count below it.  -> list of image counts; raises where the library refuses (one image too large)"""
-    lim = CONV_SPAN_LIMIT - 1
-    span0 = (batch - 1) * stride0 + c0 * hw
-    span1 = (batch - 1) * stride1 + c1 * hw if c1 else 0
-    per = batch
-    if (span0 > lim or span1 > lim) and batch > 1:
-        if stride0 > 0:
-            per = min(per, (lim - c0 * hw) // stride0 + 1)
-        if c1 and stride1 > 0:
-            per = min(per, (lim - c1 * hw) // stride1 + 1)
-    if per < 1 or c0 * hw > lim or c1 * hw > lim:
-        raise real.DevaHipError('one image of a source spans 2 GiB or more')
-    return [min(per, batch - b0) for b0 in range(0, batch, per)]
+def split_takes(pc, x0, x1, stride, pad):
+    """does a call with split run on the hi/lo split kernels?  Everything else runs the fp32 kernels although split is requested"""
+    return plan_of(pc, x0, x1, stride, pad, split=True).family == 'split'
+
+
+def wino_takes(pc, x0, x1, stride, pad, batch=None):
+    """does a call WITHOUT amp / split run on the fp32 Winograd kernel (csrc/conv_wino.hip)?  batch: of the call"""
+    return plan_of(pc, x0, x1, stride, pad, batch=batch).family == 'wino'
+
+
+def conv_sub_batches(batch, c0, h, w, stride0, c1=0, stride1=0):
+    """the sub-batches deva_conv2d runs a 3x3 / 256-output-channel call on [batch][c0 (+ c1)][h][w] sources with these
+    batch strides as (include/deva_hip.h: SIZE LIMITS), by the library's own plan: the first launch takes plan.sub_batch
+    images, the rest is planned like a call of its own.  -> list of image counts; raises where the library refuses"""
+    parts = []
+    while batch > 0:
+        plan = _real_conv_plan(c0, c1, 256, 3, pad=1, batch=batch, height=h, width=w, in0_batch_stride=stride0,
+                               in1_batch_stride=stride1)
+        parts.append(min(plan.sub_batch, batch))
+        batch -= parts[-1]
+    return parts
 
 
 _SPLIT_FALLBACKS = [0]

@@ -63,6 +63,47 @@ def test_conv_desc_mirror_has_the_c_layout(tmp_path):
     assert vals[1:] == [getattr(ConvDesc, f).offset for f in fields]
 
 
+def test_conv_plan_mirror_has_the_c_layout(tmp_path):
+    """the same probe for struct deva_conv_launch / deva_conv_plan and their ctypes mirrors, and for the family names"""
+    from deva import hip
+    launch = [f[0] for f in hip.ConvLaunch._fields_]
+    plan = [f[0] for f in hip.ConvPlan._fields_]
+    families = ['NONE', 'COUT1_TABLE', 'COUT1_ROWS', 'WINO', 'F16', 'SPLIT', 'Q4', 'IGEMM']
+    src = tmp_path / 'probe.c'
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "deva_hip.h"\nint main(void){\n'
+                   'printf("%zu\\n%zu\\n", sizeof(deva_conv_launch), sizeof(deva_conv_plan));\n' +
+                   ''.join(f'printf("%zu\\n", offsetof(deva_conv_launch, {f}));\n' for f in launch) +
+                   ''.join(f'printf("%zu\\n", offsetof(deva_conv_plan, {f}));\n' for f in plan) +
+                   ''.join(f'printf("%d\\n", DEVA_CONV_{f});\n' for f in families) +
+                   'printf("%d\\n%d\\n", DEVA_CONV_IGEMM_VEC, DEVA_CONV_IGEMM_ROW);\nreturn 0;}\n')
+    exe = tmp_path / 'probe'
+    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)], check=True)
+    vals = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert vals[:2] == [ctypes.sizeof(hip.ConvLaunch), ctypes.sizeof(hip.ConvPlan)]
+    assert vals[2:2 + len(launch)] == [getattr(hip.ConvLaunch, f).offset for f in launch]
+    assert vals[2 + len(launch):2 + len(launch) + len(plan)] == [getattr(hip.ConvPlan, f).offset for f in plan]
+    rest = vals[2 + len(launch) + len(plan):]
+    assert rest[:len(families)] == list(range(len(families))) and [f.lower() for f in families] == list(hip.CONV_FAMILIES)
+    assert rest[len(families):] == [hip.CONV_IGEMM_VEC, hip.CONV_IGEMM_ROW]
+
+
+def test_conv_plan_is_host_side(library):
+    """deva_conv2d_plan needs no device and dereferences nothing but the descriptor (made-up addresses); it refuses what
+    deva_conv2d refuses before a launch, with the same text"""
+    from deva import hip
+    from deva.hip import ops
+    L = hip.lib()
+    assert L.deva_conv2d_plan(None, None) != 0 and b'deva_conv2d_plan' in L.deva_hip_last_error()
+    plan = hip.ConvPlan()
+    assert L.deva_conv2d_plan(None, ctypes.byref(plan)) != 0 and b'null descriptor' in L.deva_hip_last_error()
+    p = ops.conv_plan(64, 0, 64, 3, pad=1, height=8, width=8)
+    assert isinstance(p, ops.ConvPlanInfo) and p.family == 'q4' and p.first.grid == (1, 2) and p.first.block == 512 and p.rerun is None
+    with pytest.raises(hip.DevaHipError, match='32-channel-slab weights need'):
+        ops.conv_plan(48, 0, 64, 3, pad=1, height=8, width=8, k_layout=hip.KLAYOUT_CHUNK32 | hip.KLAYOUT_Q4)
+    with pytest.raises(hip.DevaHipError, match='cout > 1'):
+        ops.conv_plan(64, 0, 1, 3, pad=1, height=8, width=8, k_layout=hip.KLAYOUT_Q4)
+
+
 def test_version_and_argument_errors_without_a_gpu(library):
     from deva import hip
     L = hip.lib()

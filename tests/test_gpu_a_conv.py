@@ -341,8 +341,9 @@ def test_conv_split_fallback_walks_every_tile(k, cin, cout, relu_in):
 
 
 # fp32 Winograd F(2x2, 3x3) (csrc/conv_wino.hip): the SAME 2e-5 bound as the direct kernels against the same CPU convolution, and
-# against fp64 an error of the fp32 class (measured ~2x the direct kernels').  The library takes the path only for layers with
-# >= 192 workgroups of 64 channels x 64 tiles, so the shapes are sized for that.
+# against fp64 an error of the fp32 class (measured below the direct kernels' on the network's layer shapes; bounded at 8x
+# here).  The library takes the path only for layers with >= 160 workgroups of 64 channels x 64 tiles (csrc/conv_plan.cpp),
+# so the shapes are sized for that.
 # (name, c0, c1, cout, batch, H, W, bcast0, relu_in, residual, act, bias)
 WINO_CASES = [
     ('wino_plain', 64, 0, 128, 2, 96, 128, False, False, 'none', ops.ACT_NONE, True),
@@ -397,6 +398,61 @@ def test_conv_wino_small_layers_stay_on_the_direct_kernels():
     for shape in ((1, 64, 30, 54), (4, 64, 31, 54), (64, 64, 30, 53)):
         x = _guarded(rand(g, *shape))
         assert torch.equal(ops.conv2d(pc, x, pad=1), ops.conv2d(pcd, x, pad=1)), shape
+
+
+# The plan is the launch: deva_conv2d hands splits / per_split of its plan (csrc/conv_plan.cpp) to the kernels, and a split-K
+# launch writes its partial sums to the first splits * cout * n_total floats of the workspace -- which is where a wrong
+# hand-over between plan and launcher shows without a profiler.  Guard-banded 8x8 maps, batch 1, cout 64 (whole tiles);
+# the shapes and expectations are rows of BOUNDARIES in tests/test_geometry_rules_cpu.py.
+# (name, c0, k, weights ('q4': as ops.pack_conv gives them | 'legacy': plain [K][cout_pad] | 'split'), (family, splits, per_split))
+PLAN_LAUNCH_CASES = [
+    ('q4_3x3_two_splits', 64, 3, 'q4', ('q4', 2, 12)),
+    ('q4_1x1_unsplit', 64, 1, 'q4', ('q4', 1, 2)),
+    ('legacy_7_steps_unsplit', 224, 1, 'legacy', ('igemm', 1, 7)),
+    ('legacy_8_steps_two_splits', 256, 1, 'legacy', ('igemm', 2, 4)),
+    ('split_23_steps_unsplit', 736, 1, 'split', ('split', 1, 23)),
+    ('split_24_steps_two_splits', 768, 1, 'split', ('split', 2, 12)),
+]
+_WS_SENTINEL = 0x7fc12345  # a NaN payload no sum produces
+
+
+def _legacy_pack(w, b):
+    """plain [K][cout_pad] weights (deva_conv_pack without the k-quad interleave): the round-1 kernels of conv_igemm.hip"""
+    import ctypes
+    from deva.hip import lib
+    cout, cin, kh, kw = w.shape
+    lay, cpad = ctypes.c_int(-1), ctypes.c_int(-1)
+    wc = w.contiguous()
+    n = lib().deva_conv_pack(wc.data_ptr(), None, cout, cin, kh, kw, 0, ctypes.byref(lay), ctypes.byref(cpad))
+    out = torch.empty(n)
+    assert lib().deva_conv_pack(wc.data_ptr(), out.data_ptr(), cout, cin, kh, kw, 0, ctypes.byref(lay), ctypes.byref(cpad)) == n
+    return ops.PackedConv(out.view(-1, cpad.value), b, cin, cout, cpad.value, kh, kw, lay.value)
+
+
+@pytest.mark.parametrize('case', PLAN_LAUNCH_CASES, ids=[c[0] for c in PLAN_LAUNCH_CASES])
+def test_conv_plan_is_the_launch(case):
+    name, c0, k, weights, (family, splits, per_split) = case
+    cout, H, W = 64, 8, 8
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 100000)
+    w, b = rand(g, cout, c0, k, k, scale=(2.0 / (c0 * k * k))**0.5), rand(g, cout, scale=0.1)
+    pc = _legacy_pack(w, b) if weights == 'legacy' else ops.pack_conv(w, b, None, split=weights == 'split')
+    x = rand(g, 1, c0, H, W)
+    plan = emu_ops.plan_of(pc, x, None, 1, k // 2, split=weights == 'split')
+    assert (plan.first.family, plan.first.splits, plan.first.per_split) == (family, splits, per_split), plan
+    assert plan.rerun is None or (plan.rerun.persistent and plan.rerun.splits == 1)  # (a closed gate: writes nothing)
+    want = emu_ops.conv2d(pc, x, pad=k // 2)
+    dry = os.environ.get('DEVA_TEST_DRYRUN') == '1'  # (the emulated ops have no workspace)
+    if not dry:
+        ws = ops._workspace(dev()).view(torch.int32)
+        ws.fill_(_WS_SENTINEL)
+    got = ops.conv2d(to_dev(pc), _guarded(x), pad=k // 2, split=weights == 'split')
+    torch.cuda.synchronize()
+    assert max_err(got, want) <= 2e-5 * max(1.0, want.abs().max().item())
+    if not dry:
+        written = ws != _WS_SENTINEL
+        expect = splits * cout * H * W if splits > 1 else 0
+        print(f'{name}: plan {family} splits {splits} x {per_split} K steps; workspace floats written {int(written.sum())}, expected {expect}')
+        assert bool(written[:expect].all()) and not bool(written[expect:].any()), (name, int(written.sum()), expect)
 
 
 # the 7x7 stride-2 stems on the f16 matrix pipes (csrc/conv_stem.hip): against fp64 like the split convolutions above, and

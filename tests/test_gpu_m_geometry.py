@@ -181,7 +181,7 @@ def _many_objects(net, H, W, no, chunk, P=None, alone=()):
     img_d, masks_d, sensory_d, readout_d = img.to(d), masks.to(d), sensory.to(d), readout.to(d)
     per_object = 256 * (H // 4) * (W // 4)
     print(f'{H}x{W} x{no}: the 1/4-scale 256-channel maps span {no * per_object / 2**29:.2f} x 2^29 floats -> deva_conv2d runs '
-          f'sub-batches of {emu_ops.conv_sub_batches(no, 256, (H // 4) * (W // 4), per_object)} images; '
+          f'sub-batches of {emu_ops.conv_sub_batches(no, 256, H // 4, W // 4, per_object)} images; '
           f'{no * per_object / (65535 * 16 * 256):.2f} x the threads of the pointwise kernels\' largest grid')
     one = net.segment(ms, readout_d, sensory_d, masks_d, chunk_size=-1)
     one_v = net.encode_mask(img_d, ms, sensory_d, masks_d, chunk_size=-1)

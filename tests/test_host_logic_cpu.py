@@ -468,7 +468,7 @@ def test_read_memory_matches_reference(emu, golden_dir, recipe_state_dict):
 
 
 def test_conv_tile_order_is_a_permutation():
-    """csrc/conv_epilogue.h: conv_tile_coords + csrc/conv_args.h: conv_group_m, restated line by line: for every grid
+    """csrc/conv_epilogue.h: conv_tile_coords + csrc/conv_plan.h: conv_group_m, restated line by line: for every grid
     the workgroup -> (cout tile, pixel tile) map must hit every tile exactly once, whatever the group size leaves over"""
     def group_m(taps, stride, bm, bn, tiles):
         ratio = taps * bm / (bn * stride * stride)

@@ -5,10 +5,9 @@
 #include <stdio.h>
 
 #include "deva_hip.h"
+#include "host_error.h"  // set_error, DEVA_REQUIRE
 
 namespace deva {
-
-void set_error(const char* fmt, ...);
 
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
@@ -18,14 +17,6 @@ inline int check_launch(const char* what) {
   }
   return 0;
 }
-
-#define DEVA_REQUIRE(cond, ...)    \
-  do {                             \
-    if (!(cond)) {                 \
-      deva::set_error(__VA_ARGS__); \
-      return 2;                    \
-    }                              \
-  } while (0)
 
 constexpr int kWave = 64;  // CDNA wavefront
 

@@ -318,36 +318,61 @@ __global__ __launch_bounds__(256) void conv3x3_cout1_rows2_kernel(const Cout1Arg
   }
 }
 
+// the single-channel kernels' block: the fields of ConvArgs they read
+Cout1Args cout1_args(const ConvArgs& a) {
+  Cout1Args c;
+  c.in0 = a.in0;
+  c.in1 = a.in1;
+  c.bs0 = a.bs0;
+  c.bs1 = a.bs1;
+  c.c0 = a.c0;
+  c.ctot = a.ctot;
+  c.H = a.H;
+  c.W = a.W;
+  c.OH = a.OH;
+  c.OW = a.OW;
+  c.OHW = a.OHW;
+  c.HW = a.HW;
+  c.w = a.w;
+  c.bias = a.bias;
+  c.cout_pad = a.cout_pad;
+  c.k_layout = a.k_layout;
+  c.KH = a.KH;
+  c.KW = a.KW;
+  c.stride = a.stride;
+  c.pad = a.pad;
+  c.n_total = a.n_total;
+  c.relu_in = a.relu_in;
+  c.res = a.res;
+  c.res_bs = a.res_bs;
+  c.act = a.act;
+  c.out = a.out;
+  return c;
+}
+
 }  // namespace
 
-int launch_conv3x3_cout1_rows(const Cout1Args& a, hipStream_t st) {
-  if (a.OH % 2 == 0) {
-    const int strips = (a.n_total / a.OHW) * (a.OH / 2) * (a.OW / 4);
-    hipLaunchKernelGGL(conv3x3_cout1_rows2_kernel, dim3((unsigned)ceil_div(strips, 64)), dim3(256),
-                       sizeof(float) * 9 * (size_t)a.ctot, st, a);
-    return check_launch("deva_conv2d(cout=1, 3x3 rows)");
+int launch_conv3x3_cout1_rows(const ConvArgs& a, const deva_conv_launch& l, hipStream_t st) {
+  const Cout1Args c = cout1_args(a);
+  const dim3 grid(l.grid_x), block(l.block);
+  const size_t smem = sizeof(float) * 9 * (size_t)c.ctot;
+  switch (l.kind) {
+    case 0: hipLaunchKernelGGL(conv3x3_cout1_rows2_kernel, grid, block, smem, st, c); break;  // two output rows per strip
+    case 1: hipLaunchKernelGGL(conv3x3_cout1_rows_kernel, grid, block, smem, st, c); break;
+    default: set_error("deva_conv2d(cout=1, 3x3 rows): no kernel of kind %d", l.kind); return 2;
   }
-  const int strips = a.n_total / 4;
-  hipLaunchKernelGGL(conv3x3_cout1_rows_kernel, dim3((unsigned)ceil_div(strips, 64)), dim3(256),
-                     sizeof(float) * 9 * (size_t)a.ctot, st, a);
   return check_launch("deva_conv2d(cout=1, 3x3 rows)");
 }
 
-int launch_conv_cout1(const Cout1Args& a, hipStream_t st) {
-  const int K = a.KH * a.KW * a.ctot;
-  if (a.ctot >= 65536 || a.KH >= 256 || a.KW >= 256) {
-    set_error("deva_conv2d(cout=1): channel / kernel size beyond the 16 / 8-bit table fields");
-    return 2;
-  }
-  const size_t smem = sizeof(uint2) * (((size_t)K + 63) / 64 * 64) + sizeof(float) * 256;
-  // short reductions: a wave of pixels x 4 k-groups; long ones on small maps: 8 pixels x 32 k-groups (the map is
-  // L2-resident, 32-byte runs are fine) so that ~100 k values per thread remain
-  if (K <= 512) {
-    hipLaunchKernelGGL((conv_cout1_kernel<64, 4, 8>), dim3((unsigned)ceil_div(a.n_total, 64)), dim3(256), smem, st, a);
-  } else if (a.n_total >= 8192) {
-    hipLaunchKernelGGL((conv_cout1_kernel<16, 16, 16>), dim3((unsigned)ceil_div(a.n_total, 16)), dim3(256), smem, st, a);
-  } else {
-    hipLaunchKernelGGL((conv_cout1_kernel<8, 32, 16>), dim3((unsigned)ceil_div(a.n_total, 8)), dim3(256), smem, st, a);
+int launch_conv_cout1(const ConvArgs& a, const deva_conv_launch& l, hipStream_t st) {
+  const Cout1Args c = cout1_args(a);
+  const dim3 grid(l.grid_x), block(l.block);
+  const size_t smem = sizeof(uint2) * (((size_t)a.K + 63) / 64 * 64) + sizeof(float) * 256;
+  switch (l.kind) {  // pixels x k-groups of a workgroup
+    case 0: hipLaunchKernelGGL((conv_cout1_kernel<64, 4, 8>), grid, block, smem, st, c); break;
+    case 1: hipLaunchKernelGGL((conv_cout1_kernel<16, 16, 16>), grid, block, smem, st, c); break;
+    case 2: hipLaunchKernelGGL((conv_cout1_kernel<8, 32, 16>), grid, block, smem, st, c); break;
+    default: set_error("deva_conv2d(cout=1): no kernel of kind %d", l.kind); return 2;
   }
   return check_launch("deva_conv2d(cout=1)");
 }

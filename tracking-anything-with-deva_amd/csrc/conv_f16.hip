@@ -476,8 +476,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void conv_f16_kernel(
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, int BKH, int PREC>
-int launch_tile_f16(const ConvArgs& a, int kind, hipStream_t st) {
-  ConvArgs p = a;
+int launch_tile_f16(const ConvArgs& a, const deva_conv_launch& l, hipStream_t st) {
+  ConvArgs p = conv_launch_args(a, l);
   p.gate = nullptr;
 #ifdef DEVA_CONV_PROBES
   {
@@ -488,32 +488,14 @@ int launch_tile_f16(const ConvArgs& a, int kind, hipStream_t st) {
     p.ablate = abl;
   }
 #endif
-  p.tiles_m = (int)ceil_div(a.cout, BM);
-  p.tiles_n = (int)ceil_div(a.n_total, BN);
-  const int ksteps_total = (int)ceil_div(a.K, BKH);
-  p.per_split = ksteps_total;
-  p.splits = 1;
-  const int64_t blocks = (int64_t)p.tiles_m * p.tiles_n;
-  p.group_m = conv_group_m(a.KH * a.KW, a.stride, BM, BN, blocks);
-  constexpr int STEPS_MIN = 384 / BKH;  // K steps a split must keep (6 at BKH 64)
-  if (a.ws && blocks < 192 && ksteps_total >= 2 * STEPS_MIN) {  // few tiles, long K: deterministic split-K like the fp32 kernels
-    int64_t sp = ceil_div(512, blocks);
-    if (sp > ksteps_total / STEPS_MIN) sp = ksteps_total / STEPS_MIN;
-    if (sp > 16) sp = 16;
-    const int64_t fit = a.ws_elems / ((int64_t)a.cout * a.n_total);
-    if (sp > fit) sp = fit;
-    if (sp >= 2) {
-      int per = (int)ceil_div(ksteps_total, sp);
-      if (kind == 1) per = (per + 2) / 3 * 3;
-      p.splits = (int)ceil_div(ksteps_total, per);
-      p.per_split = per;
-    }
-  }
-  const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.splits), block(64 * WAVES_M * WAVES_N);
-  if (kind == 0) {
+  const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+  if (l.kind == DEVA_CONV_KIND_1X1) {
     hipLaunchKernelGGL((conv_f16_kernel<BM, BN, WAVES_M, WAVES_N, 0, MINW, BKH, PREC>), grid, block, 0, st, p);
-  } else {
+  } else if (l.kind == DEVA_CONV_KIND_ROWS) {
     hipLaunchKernelGGL((conv_f16_kernel<BM, BN, WAVES_M, WAVES_N, 1, MINW, BKH, PREC>), grid, block, 0, st, p);
+  } else {
+    set_error("deva_conv2d: no f16 kernel of staging kind %d", l.kind);
+    return 2;
   }
   if (p.splits > 1) return launch_splitk_reduce(p, st);
   return check_launch(PREC == 2 ? "deva_conv2d (fp16 hi/lo split)" : "deva_conv2d (fp16 operands)");
@@ -521,52 +503,21 @@ int launch_tile_f16(const ConvArgs& a, int kind, hipStream_t st) {
 
 }  // namespace
 
-// -> 0 launched, 1 launch error, -1 not eligible (the caller runs the fp32 kernels)
-int launch_conv_f16(const ConvArgs& a, hipStream_t st) {
-  const int bkh = a.prec == 2 ? 32 : 64;
-  if (!a.w16 || !a.vec_ok || a.stride != 1 || a.cout < 64) return -1;
-  const bool is1x1 = a.KH == 1 && a.KW == 1;
-  // whole K steps per source; the split 1x1 kind also takes a partial LAST step (the second source's tail, or the only
-  // source's: sensory_compress 512 + 1, g4_conv 256 + 1): deva_conv_pack_split pads those weights with zeros
-  const bool tail_ok = a.prec == 2 && is1x1 && (a.c1 > 0 ? a.c0 % bkh == 0 : true);
-  if (!tail_ok && (a.c0 % bkh || a.c1 % bkh)) return -1;
-  int kind;
-  if (is1x1) {
-    kind = 0;
-  } else if (a.KH == 3 && a.KW == 3 && a.pad == 1) {
-    kind = 1;
-  } else {
-    return -1;
-  }
-  const int64_t blocks128 = ceil_div(a.cout, 128) * ceil_div(a.n_total, 128);
-  if (a.prec == 2) {
-#ifdef DEVA_CONV_PROBES  // `make PROBES=1`: A/B runs of the tile policy (tools/convlab)
-    static const int forced = [] {
-      const char* e = getenv("DEVA_SPLIT_TILE");
-      return e ? atoi(e) : 0;
-    }();
-    if (forced == 256 && a.cout >= 256) return launch_tile_f16<256, 128, 2, 4, 2, 32, 2>(a, kind, st);
-    if (forced == 128 && a.cout >= 128) return launch_tile_f16<128, 128, 2, 4, 4, 32, 2>(a, kind, st);
-    if (forced == 1284 && a.cout >= 128) return launch_tile_f16<128, 128, 2, 2, 2, 32, 2>(a, kind, st);
-    if (forced == 64) return launch_tile_f16<64, 64, 2, 2, 2, 32, 2>(a, kind, st);
+int launch_conv_f16(const ConvArgs& a, const deva_conv_launch& l, hipStream_t st) {
+  const int tile = l.bm * 1000 + l.bn;
+  if (l.family == DEVA_CONV_SPLIT && a.prec == 2) {
+    if (tile == 128128 && l.waves == 8) return launch_tile_f16<128, 128, 2, 4, 4, 32, 2>(a, l, st);
+    if (tile == 64064 && l.waves == 4) return launch_tile_f16<64, 64, 2, 2, 2, 32, 2>(a, l, st);
+#ifdef DEVA_CONV_PROBES  // `make PROBES=1`: the tiles DEVA_SPLIT_TILE can force beyond the policy's (tools/convlab)
+    if (tile == 256128 && l.waves == 8) return launch_tile_f16<256, 128, 2, 4, 2, 32, 2>(a, l, st);
+    if (tile == 128128 && l.waves == 4) return launch_tile_f16<128, 128, 2, 2, 2, 32, 2>(a, l, st);
 #endif
-    // 128x128 tiles, 8 waves (wave tile 64x32), two workgroups per CU.  Measured against it on the layers of the 480p / 5-object
-    // and the 1080p / 11-object frames (tools/convlab, DEVA_SPLIT_TILE in `make PROBES=1` builds; profiles/r05/lab): 256x128
-    // tiles (wave tile 128x32, one workgroup per CU) -1..4 %, 128x128 on four waves (wave tile 64x64) +-1 %: under real
-    // operand data the kernels run at the chip's power limit (all-zero activations: +25..34 % at an unchanged instruction
-    // stream), so fewer LDS bytes per MFMA buy nothing.
-    // (few tiles but a long K loop -- the 512 -> 512 3x3 image part of the fusers at 30x54: 52 tiles, 144 steps -- also takes
-    // the 128x128 tile: its split-K fills the chip, 45 against 72 us on 64x64 tiles)
-    // ... unless the 128x128 tiles would leave a quarter or more of the CUs without a workgroup where 64x64 tiles give every
-    // CU one (the batch-1 layers of the key encoder at 1/16 of a 1080p frame: 128 tiles of 128x128)
-    const int64_t blocks64 = ceil_div(a.cout, 64) * ceil_div(a.n_total, 64);
-    const bool half_empty = blocks128 >= 64 && blocks128 < 192 && blocks64 >= 256;
-    if (a.cout >= 128 && !half_empty && (blocks128 >= 64 || (blocks128 >= 32 && a.K >= 128 * 32)))
-      return launch_tile_f16<128, 128, 2, 4, 4, 32, 2>(a, kind, st);
-    return launch_tile_f16<64, 64, 2, 2, 2, 32, 2>(a, kind, st);
+  } else if (l.family == DEVA_CONV_F16 && a.prec == 1) {
+    if (tile == 128128 && l.waves == 8) return launch_tile_f16<128, 128, 2, 4, 4, 64, 1>(a, l, st);
+    if (tile == 64064 && l.waves == 4) return launch_tile_f16<64, 64, 2, 2, 2, 64, 1>(a, l, st);
   }
-  if (a.cout >= 128 && blocks128 >= 64) return launch_tile_f16<128, 128, 2, 4, 4, 64, 1>(a, kind, st);
-  return launch_tile_f16<64, 64, 2, 2, 2, 64, 1>(a, kind, st);
+  set_error("deva_conv2d: no f16 kernel of precision %d with a %d x %d tile on %d waves", a.prec, l.bm, l.bn, l.waves);
+  return 2;
 }
 
 }  // namespace deva

@@ -564,81 +564,18 @@ __global__ void splitk_reduce_kernel(const ConvArgs p) {
 // SPREAD: the staging of the next K step is issued during the first 1/SPREAD of the MFMA groups, the
 // rest of the step is slack for the loads to land before the LDS write.
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int SPREAD = 2>
-int launch_tile(const ConvArgs& a, hipStream_t st) {
-  ConvArgs p = a;
-  int mode;
-  if (a.KH == 1 && a.KW == 1 && a.c0 % BK == 0) {
-    mode = 0;
-  } else if (a.ctot % BK == 0 && a.c0 % BK == 0) {
-    mode = 1;
-  } else {
-    mode = 2;
-  }
-  static_assert(BK == 32, "the 32-channel-slab K layout assumes 32-deep K steps");
-  p.tiles_m = (int)ceil_div(a.cout, BM);
-  p.tiles_n = (int)ceil_div(a.n_total, BN);
-  if (a.k_layout == DEVA_KLAYOUT_CHUNK32 && mode != 1) {
-    set_error("deva_conv2d: 32-channel-slab weights need c0 and c1 to be multiples of 32");
-    return 2;
-  }
-  // split-K when the layer has too few tiles to fill the 256 CUs (small frames / single objects):
-  // partial sums go to the caller's workspace, a second kernel reduces them deterministically
-  const int ksteps_total = (int)ceil_div(a.K, BK);
-  const bool row = a.vec_ok && mode == 1 && a.KH == 3 && a.KW == 3 && a.pad == 1 &&
-                   a.k_layout == DEVA_KLAYOUT_CHUNK32 && BN / WAVES_N == 32;
-  p.per_split = ksteps_total;
-  const int64_t blocks = (int64_t)p.tiles_m * p.tiles_n;
-  p.splits = 1;
-  int64_t target_blocks = 512;
-#ifdef DEVA_CONV_PROBES
-  {
-    static const int forced = [] {
-      const char* e = getenv("DEVA_CONV_SPLIT_TARGET");  // 0 = no split-K at all
-      return e ? atoi(e) : -1;
-    }();
-    if (forced >= 0) target_blocks = forced;
-  }
-#endif
-  // measured on the batch-1 key-encoder layers (profiles/r02d_conv_small_layers.txt): the reduction launch costs
-  // ~7 us, so a layer that already has >= 128 tiles is split only when its K loop is long (>= 32 steps)
-  if (a.ws && blocks < 256 && ksteps_total >= (blocks >= 128 ? 32 : 8) && target_blocks > 0) {
-    int64_t sp = ceil_div(target_blocks, blocks);
-    if (sp > ksteps_total / 4) sp = ksteps_total / 4;
-    if (sp > 16) sp = 16;
-    const int64_t fit = a.ws_elems / ((int64_t)a.cout * a.n_total);
-    if (sp > fit) sp = fit;
-    if (sp >= 2) {
-      // every split must own at least one K step (ROW: whole groups of three)
-      int per = (int)ceil_div(ksteps_total, sp);
-      if (row) per = (per + 2) / 3 * 3;
-      sp = ceil_div(ksteps_total, per);
-      p.splits = (int)sp;
-      p.per_split = per;
-    }
-    if (p.splits < 2) p.splits = 1;
-  }
-  dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.splits);
-  const bool vec = a.vec_ok && mode != 2;
-  if (mode == 0) {
-    if (vec) {
-      hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 0, SPREAD, 1, 0>), grid, dim3(64 * WAVES_M * WAVES_N), 0, st, p);
-    } else {
-      hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 0, SPREAD, 0, 0>), grid, dim3(64 * WAVES_M * WAVES_N), 0, st, p);
-    }
-  } else if (mode == 1) {
-    if (row) {
-      if constexpr (BN / WAVES_N == 32) {
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 1, SPREAD, 1, 1>), grid, dim3(64 * WAVES_M * WAVES_N), 0, st, p);
-      }
-    } else if (vec) {
-      hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 1, SPREAD, 1, 0>), grid, dim3(64 * WAVES_M * WAVES_N), 0, st, p);
-    } else {
-      hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 1, SPREAD, 0, 0>), grid, dim3(64 * WAVES_M * WAVES_N), 0, st, p);
-    }
-  } else {
-    {
-      hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 2, SPREAD, 0, 0>), grid, dim3(64 * WAVES_M * WAVES_N), 0, st, p);
-    }
+int launch_tile(const ConvArgs& p, const deva_conv_launch& l, hipStream_t st) {
+  static_assert(BK == kConvBK, "the planner counts 32-deep K steps (the 32-channel-slab K layout assumes them too)");
+  static_assert(BN / WAVES_N == 32, "the planner hands the row reuse to every tile");
+  const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+  switch (l.kind) {
+    case 0: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 0, SPREAD, 0, 0>), grid, block, 0, st, p); break;
+    case 0 | DEVA_CONV_IGEMM_VEC: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 0, SPREAD, 1, 0>), grid, block, 0, st, p); break;
+    case 1: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 1, SPREAD, 0, 0>), grid, block, 0, st, p); break;
+    case 1 | DEVA_CONV_IGEMM_VEC: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 1, SPREAD, 1, 0>), grid, block, 0, st, p); break;
+    case 1 | DEVA_CONV_IGEMM_VEC | DEVA_CONV_IGEMM_ROW: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 1, SPREAD, 1, 1>), grid, block, 0, st, p); break;
+    case 2: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, 2, SPREAD, 0, 0>), grid, block, 0, st, p); break;
+    default: set_error("deva_conv2d: no implicit-GEMM kernel of staging kind %d", l.kind); return 2;
   }
   if (p.splits > 1) return launch_splitk_reduce(p, st);
   return check_launch("deva_conv2d");
@@ -654,327 +591,13 @@ int launch_splitk_reduce(const ConvArgs& p, hipStream_t st) {
   return check_launch("deva_conv2d");
 }
 
+int launch_conv_igemm(const ConvArgs& a, const deva_conv_launch& l, hipStream_t st) {
+  const ConvArgs p = conv_launch_args(a, l);
+  if (l.bm == 32 && l.bn == 128 && l.waves == 4) return launch_tile<32, 128, 32, 1, 4>(p, l, st);
+  if (l.bm == 64 && l.bn == 64 && l.waves == 4) return launch_tile<64, 64, 32, 2, 2>(p, l, st);
+  if (l.bm == 128 && l.bn == 128 && l.waves == 8) return launch_tile<128, 128, 32, 2, 4>(p, l, st);
+  set_error("deva_conv2d: no implicit-GEMM kernel with a %d x %d tile on %d waves", l.bm, l.bn, l.waves);
+  return 2;
+}
+
 }  // namespace deva
-
-extern "C" int deva_conv2d(const deva_conv_desc* d, void* stream) {
-  using namespace deva;
-  DEVA_REQUIRE(d != nullptr, "deva_conv2d: null descriptor");
-  DEVA_REQUIRE(d->in0 && d->weight && d->out, "deva_conv2d: null tensor");
-  DEVA_REQUIRE(d->c0 > 0 && d->c1 >= 0 && (d->c1 == 0 || d->in1), "deva_conv2d: bad channel split");
-  DEVA_REQUIRE(d->batch > 0 && d->height > 0 && d->width > 0 && d->cout > 0, "deva_conv2d: bad shape");
-  DEVA_REQUIRE(d->cout_pad % 32 == 0 && d->cout_pad >= d->cout, "deva_conv2d: cout_pad must be cout rounded up to 32");
-  DEVA_REQUIRE(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->pad >= 0, "deva_conv2d: bad kernel geometry");
-  DEVA_REQUIRE((d->k_layout & ~DEVA_KLAYOUT_Q4) == DEVA_KLAYOUT_TAP_MAJOR || (d->k_layout & ~DEVA_KLAYOUT_Q4) == DEVA_KLAYOUT_CHUNK32,
-               "deva_conv2d: unknown k_layout %d", d->k_layout);
-  // the single-channel heads (conv_cout1.hip) read column 0 of [K][cout_pad]: deva_conv_pack never interleaves them
-  DEVA_REQUIRE(!(d->cout == 1 && (d->k_layout & DEVA_KLAYOUT_Q4)), "deva_conv2d: k-quad interleaved weights need cout > 1");
-  DEVA_REQUIRE(d->amp >= 0 && d->amp <= 2, "deva_conv2d: amp must be 0 (fp32), 1 (fp16 operands) or 2 (fp16 hi/lo split)");
-  DEVA_REQUIRE(d->amp != 2 || !d->weight_f16 || d->split_flag, "deva_conv2d: the split path needs a device flag (split_flag)");
-  {
-    // the vector-gather kernels address their inputs with 32-bit byte offsets from the tensor bases: a batch whose inputs
-    // span 2 GiB or more (many objects at 4K) runs as consecutive sub-batches
-    const int64_t hw = (int64_t)d->height * d->width;
-    const int64_t lim = (1ll << 29) - 1;
-    const int64_t span0 = (int64_t)(d->batch - 1) * d->in0_batch_stride + (int64_t)d->c0 * hw;
-    const int64_t span1 = d->c1 ? (int64_t)(d->batch - 1) * d->in1_batch_stride + (int64_t)d->c1 * hw : 0;
-    if ((span0 > lim || span1 > lim) && d->batch > 1) {
-      int64_t per = d->batch;
-      if (d->in0_batch_stride > 0) per = std::min(per, (lim - (int64_t)d->c0 * hw) / d->in0_batch_stride + 1);
-      if (d->c1 && d->in1_batch_stride > 0) per = std::min(per, (lim - (int64_t)d->c1 * hw) / d->in1_batch_stride + 1);
-      if (per >= 1 && per < d->batch) {
-        const int64_t oh = (d->height + 2 * d->pad - d->kh) / d->stride + 1, ow = (d->width + 2 * d->pad - d->kw) / d->stride + 1;
-        for (int64_t b0 = 0; b0 < d->batch; b0 += per) {
-          deva_conv_desc sub = *d;
-          sub.batch = (int32_t)std::min<int64_t>(per, d->batch - b0);
-          sub.in0 = d->in0 + b0 * d->in0_batch_stride;
-          if (d->in1) sub.in1 = d->in1 + b0 * d->in1_batch_stride;
-          if (d->residual) sub.residual = d->residual + b0 * d->residual_batch_stride;
-          sub.out = d->out + b0 * (int64_t)d->cout * oh * ow;
-          const int rc = deva_conv2d(&sub, stream);
-          if (rc) return rc;
-        }
-        return 0;
-      }
-    }
-  }
-  ConvArgs a;
-  a.in0 = d->in0;
-  a.in1 = d->c1 ? d->in1 : nullptr;
-  a.bs0 = d->in0_batch_stride;
-  a.bs1 = d->in1_batch_stride;
-  a.c0 = d->c0;
-  a.c1 = d->c1;
-  a.ctot = d->c0 + d->c1;
-  a.H = d->height;
-  a.W = d->width;
-  a.OH = (d->height + 2 * d->pad - d->kh) / d->stride + 1;
-  a.OW = (d->width + 2 * d->pad - d->kw) / d->stride + 1;
-  DEVA_REQUIRE(a.OH > 0 && a.OW > 0, "deva_conv2d: empty output");
-  a.OHW = a.OH * a.OW;
-  a.HW = (int64_t)d->height * d->width;
-  a.w = d->weight;
-  a.bias = d->bias;
-  a.cout = d->cout;
-  a.cout_pad = d->cout_pad;
-  a.k_layout = d->k_layout;
-  a.KH = d->kh;
-  a.KW = d->kw;
-  a.stride = d->stride;
-  a.pad = d->pad;
-  a.K = d->kh * d->kw * a.ctot;
-  const int64_t n_total = (int64_t)d->batch * a.OHW;
-  DEVA_REQUIRE(n_total < (1ll << 31) && a.HW < (1ll << 31), "deva_conv2d: tensor too large for 32-bit pixel index");
-  a.n_total = (int)n_total;
-  a.relu_in = d->relu_in;
-  a.res = d->residual;
-  a.res_bs = d->residual_batch_stride;
-  a.act = d->act;
-  a.out = d->out;
-  a.tiles_n = 0;
-  a.tiles_m = 0;
-  a.group_m = 0;
-  {
-    const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    a.vec_out = a.OHW % 4 == 0 && al16(d->out) && (!d->residual || (al16(d->residual) && d->residual_batch_stride % 4 == 0));
-  }
-  // 4-pixel vector gathers: stride-1 'same' geometry, quads never straddle images, and the caller
-  // vouches for readable guard bands around both inputs
-  a.vec_ok = (d->stride == 1 && a.OH == a.H && a.OW == a.W && a.OHW % 4 == 0 && a.OW >= 4 &&
-              (int64_t)d->in_guard_elems >= (int64_t)d->pad * (a.W + 1) + 4)
-                 ? 1
-                 : 0;
-  a.per_split = 0;
-  a.splits = 1;
-  a.ws = d->workspace;
-  a.ws_elems = d->workspace ? d->workspace_elems : 0;
-  a.w16 = d->amp ? d->weight_f16 : nullptr;
-  a.prec = a.w16 ? d->amp : 0;
-  a.out_scale = 1.0f;
-  a.flag = nullptr;
-  a.gate = nullptr;
-  a.ablate = 0;
-  a.in0_span = (int64_t)(d->batch - 1) * a.bs0 + (int64_t)a.c0 * a.HW;
-  a.in1_span = a.in1 ? (int64_t)(d->batch - 1) * a.bs1 + (int64_t)a.c1 * a.HW : 0;
-
-  hipStream_t st = (hipStream_t)stream;
-  // single output channel: VALU kernels (conv_cout1.hip) -- a dot product per pixel on small maps
-  // (shrinkage head, CBAM gate), a row-reusing 3x3 kernel on large guard-banded maps (mask-logit head);
-  // anything else stays on the MFMA tile
-  const bool rows3x3 = a.cout == 1 && a.vec_ok && a.KH == 3 && a.KW == 3 && a.pad == 1 && a.OW % 4 == 0 &&
-                       a.n_total >= 16384 && a.ctot <= 1024 && (int64_t)d->in_guard_elems >= a.W + 8;
-  if (rows3x3 || (a.cout == 1 && a.K <= 7168 && a.n_total < 16384)) {  // 8 bytes of LDS table per reduction index
-    Cout1Args c;
-    c.in0 = a.in0;
-    c.in1 = a.in1;
-    c.bs0 = a.bs0;
-    c.bs1 = a.bs1;
-    c.c0 = a.c0;
-    c.ctot = a.ctot;
-    c.H = a.H;
-    c.W = a.W;
-    c.OH = a.OH;
-    c.OW = a.OW;
-    c.OHW = a.OHW;
-    c.HW = a.HW;
-    c.w = a.w;
-    c.bias = a.bias;
-    c.cout_pad = a.cout_pad;
-    c.k_layout = a.k_layout;
-    c.KH = a.KH;
-    c.KW = a.KW;
-    c.stride = a.stride;
-    c.pad = a.pad;
-    c.n_total = a.n_total;
-    c.relu_in = a.relu_in;
-    c.res = a.res;
-    c.res_bs = a.res_bs;
-    c.act = a.act;
-    c.out = a.out;
-    if (rows3x3) return launch_conv3x3_cout1_rows(c, st);
-    return launch_conv_cout1(c, st);
-  }
-  if (d->weight_wino && !a.w16 && a.cout > 1) {  // fp32 Winograd F(2x2, 3x3): big 3x3 stride-1 layers only (conv_wino.hip)
-    const int rc = launch_conv_wino(a, d->weight_wino, st);
-    if (rc >= 0) return rc;
-  }
-  if (a.w16 && a.cout > 1 && a.in0_span < (1ll << 29) && a.in1_span < (1ll << 29)) {
-    // opt-in f16 matrix pipes (fp16 operands, or the fp32-accurate hi/lo split): eligible shapes only, everything else
-    // -- and inputs too large for 32-bit buffer offsets -- stays on the fp32 kernels
-    // amp == 2: the gated fp32 re-run reads in0 / in1 / residual AFTER the split kernel has written `out`.  An output that
-    // overlaps one of them (an in-place residual add, say, which is fine on the plain fp32 path: every element is read
-    // before it is written by the same thread) would make the re-run add the residual twice: such calls take the fp32
-    // kernels directly (include/deva_hip.h)
-    bool aliased = false;
-    if (a.prec == 2) {
-      const auto overlaps = [&](const float* q, int64_t elems) {
-        const int64_t out_elems = (int64_t)d->batch * a.cout * a.OHW;
-        return q && elems > 0 && q < a.out + out_elems && a.out < q + elems;
-      };
-      const int64_t res_elems = d->residual ? (int64_t)(d->batch - 1) * a.res_bs + (int64_t)a.cout * a.OHW : 0;
-      aliased = overlaps(a.in0, a.in0_span) || overlaps(a.in1, a.in1_span) || overlaps(d->residual, res_elems);
-    }
-    if (a.prec == 2) {
-      DEVA_REQUIRE(d->split_scale_log2 >= -120 && d->split_scale_log2 <= 120, "deva_conv2d: split_scale_log2 out of range");
-      a.out_scale = ldexpf(1.0f, -d->split_scale_log2);
-      a.flag = d->split_flag;
-    }
-    const int rc = aliased ? -1 : launch_conv_f16(a, st);
-    if (rc > 0 || (rc == 0 && a.prec != 2)) return rc;
-    // split launched: the fp32 kernels run behind it, gated on the flag it raises for inputs beyond the fp16 range
-    if (rc == 0) a.gate = a.flag;
-#ifdef DEVA_CONV_PROBES  // `make PROBES=1`: what the gated launch costs (tools/convlab)
-    {
-      static const bool nogate = getenv("DEVA_SPLIT_NOGATE") != nullptr;
-      if (rc == 0 && nogate) return 0;
-    }
-#endif
-  }
-  a.w16 = nullptr;
-  a.prec = 0;
-  a.out_scale = 1.0f;
-  a.flag = nullptr;
-  if (a.k_layout & DEVA_KLAYOUT_Q4) {
-    // buffer addressing: 32-bit byte offsets from the tensor bases
-    DEVA_REQUIRE(a.in0_span < (1ll << 29) && a.in1_span < (1ll << 29),
-                 "deva_conv2d: one image of a source spans 2 GiB or more (32-bit buffer offsets; larger BATCHES run as sub-batches)");
-    if (a.gate) {  // the re-run behind a split launch: a persistent kernel (what it costs is its dispatch)
-      const int rc = launch_conv_q4_gated(a, st);
-      if (rc >= 0) return rc;
-    }
-    return launch_conv_q4(a, st);
-  }
-  // Tile choice (all tiles run 32-deep K steps):
-  const int64_t blocks128 = ceil_div(a.cout, 128) * ceil_div(a.n_total, 128);
-#ifdef DEVA_CONV_PROBES  // `make PROBES=1`: A/B runs of the tile policy (tools/conv_microbench.py)
-  {
-    static const int forced = [] {
-      const char* e = getenv("DEVA_CONV_TILE");
-      return e ? atoi(e) : 0;
-    }();
-    if (forced == 64 && a.cout > 32) return launch_tile<64, 64, 32, 2, 2>(a, st);
-    if (forced == 128 && a.cout >= 128) return launch_tile<128, 128, 32, 2, 4>(a, st);
-  }
-#endif
-  if (a.cout <= 32) return launch_tile<32, 128, 32, 1, 4>(a, st);
-  // measured: the 8-wave 128x128 tile beats the 64x64 tile from ~64 tiles up (split-K tops the grid up)
-  // ... except where the 128-wide tiles would need split-K while the 64-wide ones fill the chip on their own
-  // (1x1 256->1024 on a 30x54 map: 20 vs 29 us)
-  const int64_t blocks64 = ceil_div(a.cout, 64) * ceil_div(a.n_total, 64);
-  if (a.cout >= 128 && blocks128 >= 64 && !(blocks128 < 256 && blocks64 >= 256 && a.K <= 512))
-    return launch_tile<128, 128, 32, 2, 4>(a, st);
-  return launch_tile<64, 64, 32, 2, 2>(a, st);
-}
-
-// Host-side weight packing (model load, not the frame path): [cout][cin][kh][kw] -> the layout deva_conv2d reads.
-extern "C" int64_t deva_conv_pack(const float* w_oihw, float* out, int cout, int cin, int kh, int kw, int want_q4,
-                                  int* k_layout, int* cout_pad_out) {
-  using namespace deva;
-  if (!w_oihw || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0 || !k_layout || !cout_pad_out) {
-    set_error("deva_conv_pack: bad arguments");
-    return -1;
-  }
-  const int taps = kh * kw;
-  const int K = taps * cin;
-  const int cout_pad = (cout + 31) / 32 * 32;
-  const bool chunk = taps > 1 && cin % 32 == 0;
-  const bool q4 = want_q4 && cout > 1;  // the single-channel heads (conv_cout1.hip) read column 0 of [K][cout_pad]
-  const int64_t rows = q4 ? (int64_t)(K + 3) / 4 * 4 : K;
-  const int64_t elems = rows * cout_pad;
-  *k_layout = (chunk ? DEVA_KLAYOUT_CHUNK32 : DEVA_KLAYOUT_TAP_MAJOR) | (q4 ? DEVA_KLAYOUT_Q4 : 0);
-  *cout_pad_out = cout_pad;
-  if (!out) return elems;
-  for (int64_t i = 0; i < elems; ++i) out[i] = 0.0f;
-  for (int m = 0; m < cout; ++m)
-    for (int c = 0; c < cin; ++c)
-      for (int t = 0; t < taps; ++t) {
-        const int64_t k = chunk ? ((int64_t)(c / 32) * taps + t) * 32 + c % 32 : (int64_t)t * cin + c;
-        const int64_t at = q4 ? ((k >> 2) * cout_pad + m) * 4 + (k & 3) : k * cout_pad + m;
-        out[at] = w_oihw[((int64_t)m * cin + c) * taps + t];
-      }
-  return elems;
-}
-
-// fp16 weights of the opt-in amp path (host side, model load): element (k, m) at ((k/8)*cout_pad + m)*8 + k%8, IEEE
-// binary16 bits, round to nearest even; K order: tap-major for 1x1, 64-channel slabs otherwise
-// (k = ((c/64)*taps + tap)*64 + c%64; needs cin % 64 == 0, else -1: the layer stays fp32).
-extern "C" int64_t deva_conv_pack_f16(const float* w_oihw, uint16_t* out, int cout, int cin, int kh, int kw, int* cout_pad_out) {
-  using namespace deva;
-  if (!w_oihw || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0 || !cout_pad_out) {
-    set_error("deva_conv_pack_f16: bad arguments");
-    return -1;
-  }
-  const int taps = kh * kw;
-  if (cin % 64 != 0) return -1;
-  const int K = taps * cin;
-  const int cout_pad = (cout + 31) / 32 * 32;
-  const int64_t elems = (int64_t)K * cout_pad;
-  *cout_pad_out = cout_pad;
-  if (!out) return elems;
-  for (int64_t i = 0; i < elems; ++i) out[i] = 0;
-  for (int m = 0; m < cout; ++m)
-    for (int c = 0; c < cin; ++c)
-      for (int t = 0; t < taps; ++t) {
-        const int64_t k = taps > 1 ? ((int64_t)(c / 64) * taps + t) * 64 + c % 64 : c;
-        const _Float16 h = (_Float16)w_oihw[((int64_t)m * cin + c) * taps + t];
-        uint16_t bits;
-        __builtin_memcpy(&bits, &h, 2);
-        out[((k >> 3) * cout_pad + m) * 8 + (k & 7)] = bits;
-      }
-  return elems;
-}
-
-// hi / lo fp16 planes of the split path (host side, model load): with s = 2^e, e such that the largest |w| * s lies in
-// [2^13, 2^14) (e = 0 for an all-zero layer), hi = fp16(w s), lo = fp16(w s - hi) (round to nearest even; w s and the
-// difference are exact in fp32), element (k, plane, m) at (((k/8)*2 + plane)*cout_pad + m)*8 + k%8; K order: tap-major
-// for 1x1 (any cin: K is padded with zero rows to a multiple of 32), 32-channel slabs otherwise
-// (k = ((c/32)*taps + tap)*32 + c%32; needs cin % 32 == 0, else -1: the layer stays on the fp32 kernels).
-// *scale_log2 = e; deva_conv2d multiplies the accumulators by 2^-e.
-extern "C" int64_t deva_conv_pack_split(const float* w_oihw, uint16_t* out, int cout, int cin, int kh, int kw, int* cout_pad_out,
-                                        int* scale_log2) {
-  using namespace deva;
-  if (!w_oihw || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0 || !cout_pad_out || !scale_log2) {
-    set_error("deva_conv_pack_split: bad arguments");
-    return -1;
-  }
-  const int taps = kh * kw;
-  if (cin % 32 != 0 && taps > 1) return -1;
-  const int K = (taps * cin + 31) / 32 * 32;  // 1x1 layers with a channel tail (513, 257): zero rows up to the next K step
-  const int cout_pad = (cout + 31) / 32 * 32;
-  const int64_t elems = (int64_t)K * 2 * cout_pad;
-  *cout_pad_out = cout_pad;
-  float wmax = 0.0f;
-  const int64_t n = (int64_t)cout * cin * taps;
-  for (int64_t i = 0; i < n; ++i) {
-    const float v = fabsf(w_oihw[i]);
-    if (!(v <= 3.0e38f)) {
-      set_error("deva_conv_pack_split: non-finite weight");
-      return -1;
-    }
-    if (v > wmax) wmax = v;
-  }
-  int e = 0;
-  if (wmax > 0.0f) {
-    int x;
-    frexpf(wmax, &x);  // wmax = f * 2^x, f in [0.5, 1)
-    e = 14 - x;
-    if (e > 120) e = 120;
-    if (e < -120) e = -120;
-  }
-  *scale_log2 = e;
-  if (!out) return elems;
-  for (int64_t i = 0; i < elems; ++i) out[i] = 0;
-  for (int m = 0; m < cout; ++m)
-    for (int c = 0; c < cin; ++c)
-      for (int t = 0; t < taps; ++t) {
-        const int64_t k = taps > 1 ? ((int64_t)(c / 32) * taps + t) * 32 + c % 32 : c;
-        const float ws = ldexpf(w_oihw[((int64_t)m * cin + c) * taps + t], e);
-        const _Float16 hi = (_Float16)ws;
-        const _Float16 lo = (_Float16)(ws - (float)hi);
-        uint16_t bh, bl;
-        __builtin_memcpy(&bh, &hi, 2);
-        __builtin_memcpy(&bl, &lo, 2);
-        out[(((k >> 3) * 2 + 0) * cout_pad + m) * 8 + (k & 7)] = bh;
-        out[(((k >> 3) * 2 + 1) * cout_pad + m) * 8 + (k & 7)] = bl;
-      }
-  return elems;
-}

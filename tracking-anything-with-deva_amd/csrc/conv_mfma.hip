@@ -74,7 +74,7 @@ __device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, int voff, i
 // only when the split kernel met an input beyond the fp16 range -- practically never --, so what it costs is the dispatch
 // of its workgroups, each of which reads the flag and leaves: 4.5-6 us per layer at 1080p / 11 objects with one workgroup
 // per tile (~8 000 of them, at one or two per CU for the LDS they reserve).  The persistent form is launched with at most
-// PERSIST_MAX_WGS workgroups that walk over the tiles (stride gridDim.x, a multiple of 8: a workgroup stays on its XCD's
+// kPersistMaxWgs (conv_plan.h) workgroups that walk over the tiles (stride gridDim.x, a multiple of 8: a workgroup stays on its XCD's
 // tiles); same arithmetic, same K order as every other WK = 1 / unsplit variant.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int KIND, int MINW, int WK, int RELU, bool PERSIST = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WK, (KIND <= 1 || MINW < 2) ? MINW : 2) void conv_mfma_kernel(const ConvArgs p) {
@@ -553,119 +553,49 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WK, (KIND <= 1 || MINW < 2
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, int WK = 1>
-int launch_tile_q4(const ConvArgs& a, hipStream_t st) {
-  ConvArgs p = a;
-  const bool uniform = a.ctot % BK == 0 && a.c0 % BK == 0;  // tap and source uniform per K step
-  int kind;
-  if (a.vec_ok && a.KH == 1 && a.KW == 1 && a.c0 % BK == 0) {
-    kind = 0;
-  } else if (a.vec_ok && uniform && a.KH == 3 && a.KW == 3 && a.pad == 1 && (a.k_layout & 0xf) == DEVA_KLAYOUT_CHUNK32 &&
-             BN / WAVES_N == 32) {
-    kind = 1;
-  } else if (uniform) {
-    kind = 2;
-  } else {
-    kind = 3;
-  }
-  if ((a.k_layout & 0xf) == DEVA_KLAYOUT_CHUNK32 && !uniform) {
-    set_error("deva_conv2d: 32-channel-slab weights need c0 and c1 to be multiples of 32");
-    return 2;
-  }
-  p.tiles_m = (int)ceil_div(a.cout, BM);
-  p.tiles_n = (int)ceil_div(a.n_total, BN);
-  const int ksteps_total = (int)ceil_div(a.K, BK);
-  p.per_split = ksteps_total;
-  const int blocks_eff_scale = WK;  // every workgroup already holds WK slice groups
-  const int64_t blocks = (int64_t)p.tiles_m * p.tiles_n;
-  p.group_m = conv_group_m(a.KH * a.KW, a.stride, BM, BN, blocks);
-  p.splits = 1;
-  int64_t target_blocks = 512;
-  // measured (tools/convlab sweep, profiles/r04a): from ~190 tiles up the split (+ its reduction pass) loses
-  bool want_split = a.ws && blocks < 192 && ksteps_total >= (blocks >= 128 ? 32 : 8);
-#ifdef DEVA_CONV_PROBES
-  {
-    static const int forced = [] {
-      const char* e = getenv("DEVA_CONV_SPLIT_TARGET");  // blocks to aim for; 0 = no split-K at all
-      return e ? atoi(e) : -1;
-    }();
-    static const int forced_group = [] {
-      const char* e = getenv("DEVA_CONV_GROUP_M");  // cout tiles per tile-order group; 0 = all
-      return e ? atoi(e) : -1;
-    }();
-    if (forced_group >= 0) p.group_m = forced_group;
-    if (forced == 0) want_split = false;
-    if (forced > 0) {
-      target_blocks = forced;
-      want_split = a.ws && blocks < forced;
-    }
-  }
-#endif
-  if (want_split) {
-    int64_t sp = ceil_div(target_blocks, blocks * blocks_eff_scale);
-    if (sp > ksteps_total / (4 * WK)) sp = ksteps_total / (4 * WK);
-    if (sp > 16) sp = 16;
-    const int64_t fit = a.ws_elems / ((int64_t)a.cout * a.n_total);
-    if (sp > fit) sp = fit;
-    if (sp >= 2) {
-      int per = (int)ceil_div(ksteps_total, sp);
-      if (kind == 1) per = (per + 3 * WK - 1) / (3 * WK) * (3 * WK);  // row reuse: whole (slab, dy) groups per slice group
-      sp = ceil_div(ksteps_total, per);
-      p.splits = (int)sp;
-      p.per_split = per;
-    }
-    if (p.splits < 2) p.splits = 1;
-  }
-  const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), (unsigned)p.splits), block(64 * WAVES_M * WAVES_N * WK);
-  if constexpr (BM == 128 && WK > 1) {
-    if (kind >= 2) return launch_tile_q4<BM, BN, WAVES_M, WAVES_N, MINW, 1>(a, st);  // scalar kinds: no K-slice build at 1024 threads
-  }
-  switch (kind) {
-    case 0: hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 0, MINW, WK, 1>), grid, block, 0, st, p); break;
-    case 1:
-      if constexpr (BN / WAVES_N == 32) {
-        if (p.relu_in) hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 1, MINW, WK, 2>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 1, MINW, WK, 0>), grid, block, 0, st, p);
+int launch_tile_q4(const ConvArgs& p, const deva_conv_launch& l, hipStream_t st) {
+  static_assert(BN / WAVES_N == 32, "the planner hands the row reuse to every tile");
+  const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+  constexpr bool SCALAR_KINDS = !(BM == 128 && WK > 1);  // no K-slice build of the scalar kinds at 1024 threads
+  switch (l.kind) {
+    case DEVA_CONV_KIND_1X1: hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 0, MINW, WK, 1>), grid, block, 0, st, p); break;
+    case DEVA_CONV_KIND_ROWS:
+      if (p.relu_in) hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 1, MINW, WK, 2>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 1, MINW, WK, 0>), grid, block, 0, st, p);
+      break;
+    case DEVA_CONV_KIND_UNIFORM:
+      if constexpr (SCALAR_KINDS) {
+        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 2, MINW, WK, 1>), grid, block, 0, st, p);
+        break;
       }
-      break;
-    case 2:
-      if constexpr (!(BM == 128 && WK > 1)) hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 2, MINW, WK, 1>), grid, block, 0, st, p);
-      break;
+      [[fallthrough]];
+    case DEVA_CONV_KIND_GENERIC:
+      if constexpr (SCALAR_KINDS) {
+        hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 3, MINW, WK, 1>), grid, block, 0, st, p);
+        break;
+      }
+      [[fallthrough]];
     default:
-      if constexpr (!(BM == 128 && WK > 1)) hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WAVES_M, WAVES_N, 3, MINW, WK, 1>), grid, block, 0, st, p);
-      break;
+      set_error("deva_conv2d: no fp32 MFMA kernel of staging kind %d for a %d x %d tile with %d K-slice groups", l.kind, BM, BN, WK);
+      return 2;
   }
   if (p.splits > 1) return launch_splitk_reduce(p, st);
   return check_launch("deva_conv2d");
 }
 
-constexpr int PERSIST_MAX_WGS = 1024;  // workgroups of a gated re-run (a multiple of 8; 4 per CU fit: 35 KB of LDS each)
+static_assert(BK == kConvBK, "the planner counts K steps of this depth");
 
 }  // namespace
 
-// The fp32 re-run behind a split launch, gated on the flag the split kernel raises (a.gate): persistent 64x64 tiles for
-// the two kinds the split kernels take (1x1 and 3x3 stride 1 on guard-banded inputs); -1 = not one of those, the caller
-// launches the regular kernels with the gate.  No split-K, no K slices: when the gate opens, the result is the fp32
-// kernels' in their plain K order (bit-identical to every unsplit WK = 1 variant).
-int launch_conv_q4_gated(const ConvArgs& a, hipStream_t st) {
+int launch_conv_q4_gated(const ConvArgs& a, const deva_conv_launch& l, hipStream_t st) {
   constexpr int BM = 64, BN = 64;
-  if (!a.gate || !a.vec_ok || a.cout <= 32 || a.c0 % BK) return -1;
-  int kind;
-  if (a.KH == 1 && a.KW == 1) {
-    kind = 0;
-  } else if (a.ctot % BK == 0 && a.KH == 3 && a.KW == 3 && a.pad == 1 && (a.k_layout & 0xf) == DEVA_KLAYOUT_CHUNK32) {
-    kind = 1;
-  } else {
-    return -1;
+  const ConvArgs p = conv_launch_args(a, l);
+  const dim3 grid(l.grid_x), block(l.block);
+  if (l.bm != BM || l.bn != BN || l.waves != 4 || l.wk != 1 || l.splits != 1 || l.kind > DEVA_CONV_KIND_ROWS) {
+    set_error("deva_conv2d: no persistent fp32 MFMA kernel of staging kind %d for a %d x %d tile", l.kind, l.bm, l.bn);
+    return 2;
   }
-  ConvArgs p = a;
-  p.tiles_m = (int)ceil_div(a.cout, BM);
-  p.tiles_n = (int)ceil_div(a.n_total, BN);
-  p.per_split = (int)ceil_div(a.K, BK);
-  p.splits = 1;
-  const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n;
-  p.group_m = conv_group_m(a.KH * a.KW, a.stride, BM, BN, tiles);
-  const dim3 grid((unsigned)(tiles < PERSIST_MAX_WGS ? tiles : PERSIST_MAX_WGS)), block(256);
-  if (kind == 0) {
+  if (l.kind == DEVA_CONV_KIND_1X1) {
     hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, 2, 2, 0, 1, 1, 1, true>), grid, block, 0, st, p);
   } else if (p.relu_in) {
     hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, 2, 2, 1, 1, 1, 2, true>), grid, block, 0, st, p);
@@ -675,43 +605,25 @@ int launch_conv_q4_gated(const ConvArgs& a, hipStream_t st) {
   return check_launch("deva_conv2d (gated fp32 re-run)");
 }
 
-int launch_conv_q4(const ConvArgs& a, hipStream_t st) {
-#ifdef DEVA_CONV_PROBES  // `make PROBES=1`: A/B runs of the tile policy (tools/convlab)
-  {
-    static const int forced = [] {
-      const char* e = getenv("DEVA_CONV_TILE");
-      return e ? atoi(e) : 0;
-    }();
-    switch (forced) {
-      case 128: if (a.cout >= 64) return launch_tile_q4<128, 128, 2, 4, 4>(a, st); break;
-      case 64: if (a.cout > 32) return launch_tile_q4<64, 64, 2, 2, 1>(a, st); break;
-      case 642: if (a.cout > 32) return launch_tile_q4<64, 64, 2, 2, 1, 2>(a, st); break;
-      case 644: if (a.cout > 32) return launch_tile_q4<64, 64, 2, 2, 1, 4>(a, st); break;
-      case 1282: if (a.cout >= 64) return launch_tile_q4<128, 128, 2, 4, 4, 2>(a, st); break;
-      case 12864: if (a.cout >= 64) return launch_tile_q4<128, 64, 2, 2, 2>(a, st); break;
-      case 64128: if (a.cout > 32) return launch_tile_q4<64, 128, 1, 4, 2>(a, st); break;
-      default: break;
-    }
+int launch_conv_q4(const ConvArgs& a, const deva_conv_launch& l, hipStream_t st) {
+  const ConvArgs p = conv_launch_args(a, l);
+  const int tile = l.bm * 1000 + l.bn;
+  if (tile == 32128 && l.waves == 4 && l.wk == 1) return launch_tile_q4<32, 128, 1, 4, 1>(p, l, st);
+  if (tile == 64064 && l.waves == 4) {
+    if (l.wk == 1) return launch_tile_q4<64, 64, 2, 2, 1>(p, l, st);
+    if (l.wk == 2) return launch_tile_q4<64, 64, 2, 2, 1, 2>(p, l, st);
+    if (l.wk == 4) return launch_tile_q4<64, 64, 2, 2, 1, 4>(p, l, st);
   }
+  if (tile == 128128 && l.waves == 8) {
+    if (l.wk == 1) return launch_tile_q4<128, 128, 2, 4, 4>(p, l, st);
+    if (l.wk == 2) return launch_tile_q4<128, 128, 2, 4, 4, 2>(p, l, st);
+  }
+#ifdef DEVA_CONV_PROBES  // `make PROBES=1`: the tiles DEVA_CONV_TILE can force beyond the policy's (tools/convlab)
+  if (tile == 128064 && l.waves == 4 && l.wk == 1) return launch_tile_q4<128, 64, 2, 2, 2>(p, l, st);
+  if (tile == 64128 && l.waves == 4 && l.wk == 1) return launch_tile_q4<64, 128, 1, 4, 2>(p, l, st);
 #endif
-  if (a.cout <= 32) return launch_tile_q4<32, 128, 1, 4, 1>(a, st);
-  // Tile policy (warm sweeps over the layers of the 480p frame, tools/convlab/sweep.sh, profiles/r04a):
-  //  * 128x128 (8 waves, wave tile 64x32) from 64 tiles up -- unless it would leave most CUs empty while 64x64 tiles
-  //    fill the chip; with at most one tile per CU the workgroup carries two K-slice groups (16 waves per CU);
-  //  * 64x64 (4 waves) otherwise; layers with few tiles and a long K loop run 2 or 4 K-slice groups per workgroup.
-  const int64_t blocks128 = ceil_div(a.cout, 128) * ceil_div(a.n_total, 128);
-  const int64_t blocks64 = ceil_div(a.cout, 64) * ceil_div(a.n_total, 64);
-  const int ksteps = (int)ceil_div(a.K, BK);
-  const bool vec_kind = a.vec_ok && a.c0 % BK == 0 &&
-                        ((a.KH == 1 && a.KW == 1) || (a.ctot % BK == 0 && a.KH == 3 && a.KW == 3 && a.pad == 1 &&
-                                                      (a.k_layout & 0xf) == DEVA_KLAYOUT_CHUNK32));
-  if (a.cout >= 128 && blocks128 >= 64 && !(blocks128 < 192 && blocks64 >= 256)) {
-    if (vec_kind && blocks128 <= 256 && ksteps >= 16) return launch_tile_q4<128, 128, 2, 4, 4, 2>(a, st);
-    return launch_tile_q4<128, 128, 2, 4, 4>(a, st);
-  }
-  if (ksteps >= 32 && blocks64 >= 64 && blocks64 <= 208) return launch_tile_q4<64, 64, 2, 2, 1, 4>(a, st);
-  if ((ksteps >= 16 && blocks64 <= 208) || (ksteps >= 32 && blocks64 <= 512)) return launch_tile_q4<64, 64, 2, 2, 1, 2>(a, st);
-  return launch_tile_q4<64, 64, 2, 2, 1>(a, st);
+  set_error("deva_conv2d: no fp32 MFMA kernel with a %d x %d tile on %d waves and %d K-slice groups", l.bm, l.bn, l.waves, l.wk);
+  return 2;
 }
 
 }  // namespace deva

@@ -528,12 +528,9 @@ __global__ __launch_bounds__(512, 1) void conv_wino_kernel(const WinoArgs p) {
 
 }  // namespace
 
-// -> 0 launched, 1 launch error, -1 not eligible (the caller runs the direct kernels)
-int launch_conv_wino(const ConvArgs& a, const float* u, hipStream_t st) {
-  if (!u || !a.vec_ok || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || (a.W & 1) || a.W < 4) return -1;  // (odd heights: a last tile row of one output row)
-  if (a.c0 % KC || a.ctot % KC || a.cout < 32) return -1;
-  if (a.in0_span >= (1ll << 29) || a.in1_span >= (1ll << 29)) return -1;  // 32-bit byte offsets inside a source (buffer loads)
-  if (a.res && (int64_t)(a.n_total / a.OHW) * a.res_bs >= (1ll << 29)) return -1;  // ... and inside the residual
+static_assert(KC == kWinoKC && WM == kWinoBM && WN == kWinoBN, "what the planner assumes of this kernel");
+
+int launch_conv_wino(const ConvArgs& a, const float* u, const deva_conv_launch& l, hipStream_t st) {
   WinoArgs p;
   p.in0 = a.in0;
   p.in1 = a.in1 ? a.in1 : a.in0;
@@ -565,24 +562,12 @@ int launch_conv_wino(const ConvArgs& a, const float* u, hipStream_t st) {
   }();
   p.ablate = ablate_probe;
 #endif
-  p.by_tiles = (int64_t)batch * a.HW > 16ll * p.cout_pad;  // activation elements per channel > transformed weights per channel
-#if defined(DEVA_CONV_PROBES) || defined(DEVA_WINO_TUNE)  // (`make EXTRA=-DDEVA_WINO_TUNE`: the threshold alone, kernels as shipped)
-  static const int min_blocks_probe = [] {
-    const char* e = getenv("DEVA_WINO_MIN_BLOCKS");
-    return e ? atoi(e) : 160;
-  }();
-  const int min_blocks = min_blocks_probe;
-  static const int by_tiles_probe = [] {
-    const char* e = getenv("DEVA_WINO_BY_TILES");
-    return e ? atoi(e) : -1;
-  }();
-  if (by_tiles_probe >= 0) p.by_tiles = by_tiles_probe;
-#else
-  const int min_blocks = 160;
-#endif
-  const int64_t blocks = (int64_t)p.blocks_m * ceil_div(p.n_tiles, WN);
-  if (blocks < min_blocks) return -1;  // one workgroup per CU: fewer than ~2/3 of the CUs and the direct kernels' split-K wins
-  const dim3 grid((unsigned)blocks), block(512);
+  p.by_tiles = l.kind;
+  if (p.blocks_m != l.tiles_m || (int64_t)l.tiles_m * l.tiles_n != l.grid_x) {
+    set_error("deva_conv2d: the plan's Winograd grid (%d x %d) does not fit the kernel's %d cout blocks", l.tiles_m, l.tiles_n, p.blocks_m);
+    return 2;
+  }
+  const dim3 grid(l.grid_x), block(l.block);
   if (p.relu_in) {
     if (p.res) {
       hipLaunchKernelGGL((conv_wino_kernel<true, true>), grid, block, 0, st, p);

@@ -1,0 +1,17 @@
+// Error reporting of libdeva_hip.so for host code: no HIP in here, so the translation units that only decide or pack
+// (conv_plan.cpp, conv_pack.cpp) compile with the host compiler alone.  common.h includes it for everything else.
+#pragma once
+
+namespace deva {
+
+void set_error(const char* fmt, ...);  // runtime.hip; text behind deva_hip_last_error()
+
+#define DEVA_REQUIRE(cond, ...)    \
+  do {                             \
+    if (!(cond)) {                 \
+      deva::set_error(__VA_ARGS__); \
+      return 2;                    \
+    }                              \
+  } while (0)
+
+}  // namespace deva

@@ -6,7 +6,7 @@ wrapper in `ops.py` raises if handed a tensor that is not a contiguous fp32 HIP 
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libdeva_hip.so')
@@ -40,6 +40,26 @@ class ConvDesc(Structure):
     ]
 
 
+# kernel families of a convolution plan (include/deva_hip.h: DEVA_CONV_*), by value
+CONV_FAMILIES = ('none', 'cout1_table', 'cout1_rows', 'wino', 'f16', 'split', 'q4', 'igemm')
+CONV_IGEMM_VEC, CONV_IGEMM_ROW = 4, 8
+
+
+class ConvLaunch(Structure):
+    """mirror of `struct deva_conv_launch` (include/deva_hip.h)"""
+    _fields_ = [
+        ('family', c_int32), ('bm', c_int32), ('bn', c_int32), ('waves', c_int32), ('wk', c_int32), ('kind', c_int32),
+        ('persistent', c_int32), ('tiles_m', c_int32), ('tiles_n', c_int32),
+        ('splits', c_int32), ('per_split', c_int32), ('group_m', c_int32),
+        ('grid_x', c_uint32), ('grid_y', c_uint32), ('block', c_uint32),
+    ]
+
+
+class ConvPlan(Structure):
+    """mirror of `struct deva_conv_plan` (include/deva_hip.h)"""
+    _fields_ = [('first', ConvLaunch), ('rerun', ConvLaunch), ('aliased', c_int32), ('sub_batch', c_int32)]
+
+
 ENSEMBLE_MAX_VARIANTS = 8
 
 
@@ -58,6 +78,7 @@ SIGNATURES = {
     'deva_hip_version': (c_int, []),
     'deva_hip_last_error': (c_char_p, []),
     'deva_conv2d': (c_int, [POINTER(ConvDesc), c_void_p]),
+    'deva_conv2d_plan': (c_int, [POINTER(ConvDesc), POINTER(ConvPlan)]),
     'deva_conv_pack_f16': (c_int64, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int)]),
     'deva_conv_pack_split': (c_int64, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     'deva_conv_pack_wino': (c_int64, [c_void_p, c_void_p, c_int, c_int]),

@@ -11,10 +11,10 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from . import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SQUARE_PLUS_ONE, ENSEMBLE_MAX_VARIANTS, KLAYOUT_CHUNK32, KLAYOUT_Q4,
-               KLAYOUT_TAP_MAJOR, ConvDesc, DevaHipError, EnsembleVariant, check, lib)
+from . import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SQUARE_PLUS_ONE, CONV_FAMILIES, ENSEMBLE_MAX_VARIANTS, KLAYOUT_CHUNK32,
+               KLAYOUT_Q4, KLAYOUT_TAP_MAJOR, ConvDesc, ConvPlan, DevaHipError, EnsembleVariant, check, lib)
 
-__all__ = ['PackedConv', 'pack_conv', 'conv2d', 'split_fallbacks', 'PackedStem', 'pack_stem', 'stem7x7', 'pad2d', 'usage_init', 'gather_s2', 'maxpool3x3s2', 'upsample2x_add', 'upsample2x_add_ds2', 'clip_index', 'upsample2x_add_map', 'upsample2x_add_ds2_map', 'area_downsample',
+__all__ = ['PackedConv', 'pack_conv', 'conv2d', 'conv_plan', 'ConvLaunchInfo', 'ConvPlanInfo', 'split_fallbacks', 'PackedStem', 'pack_stem', 'stem7x7', 'pad2d', 'usage_init', 'gather_s2', 'maxpool3x3s2', 'upsample2x_add', 'upsample2x_add_ds2', 'clip_index', 'upsample2x_add_map', 'upsample2x_add_ds2_map', 'area_downsample',
            'aggregate', 'softmax_channels', 'upsample4x_softmax', 'cbam', 'gru_update',
            'affinity_topk', 'BankPrep', 'affinity_dense', 'dense_read', 'affinity_candidates', 'affinity_merge', 'usage_update', 'readout_sparse', 'bank_append', 'bank_gather_rows',
            'bank_export', 'rank', 'rank_select', 'evict_select', 'similarity_dense', 'softmax_columns',
@@ -370,6 +370,81 @@ def conv2d(pc: PackedConv, x0: torch.Tensor, x1: Optional[torch.Tensor] = None, 
     d.weight_wino = _p(pc.weight_wino, name='Winograd weight') if (pc.weight_wino is not None and d.amp == 0) else None
     check(lib().deva_conv2d(d, _stream()), 'deva_conv2d')
     return out
+
+
+class ConvLaunchInfo(NamedTuple):
+    """one launch of a convolution plan (include/deva_hip.h: deva_conv_launch)"""
+    family: str          # one of CONV_FAMILIES
+    tile: Tuple[int, int]
+    waves: int
+    wk: int
+    kind: int
+    persistent: bool
+    splits: int
+    per_split: int
+    group_m: int
+    grid: Tuple[int, int]
+    block: int
+
+
+class ConvPlanInfo(NamedTuple):
+    """what deva_conv2d launches for a call (include/deva_hip.h: deva_conv_plan)"""
+    first: ConvLaunchInfo
+    rerun: Optional[ConvLaunchInfo]  # the gated fp32 launch behind a hi/lo split launch
+    aliased: bool
+    sub_batch: int
+
+    @property
+    def family(self) -> str:
+        return self.first.family
+
+
+# made-up, well separated and 16-byte aligned addresses of conv_plan's operands (deva_conv2d_plan dereferences none)
+_PLAN_ADDRESSES = dict(in0=1 << 40, in1=2 << 40, residual=3 << 40, out=4 << 40)
+
+
+def conv_plan(c0: int, c1: int, cout: int, kh: int, kw: Optional[int] = None, *, stride: int = 1, pad: int = 0, batch: int = 1,
+              height: int, width: int, k_layout: Optional[int] = None, weights: Tuple[str, ...] = (), amp: bool = False,
+              split: bool = False, guard: int = GUARD, workspace_elems: int = _WORKSPACE_ELEMS, in0_batch_stride: Optional[int] = None,
+              in1_batch_stride: Optional[int] = None, residual: bool = False, residual_batch_stride: Optional[int] = None,
+              relu_in: bool = False, addresses: Optional[dict] = None) -> ConvPlanInfo:
+    """The library's plan for a `conv2d` call of this shape (deva_conv2d_plan: the function deva_conv2d itself plans with).
+    Allocates nothing and needs no device.  k_layout: default what `pack_conv` gives the layer; weights: which optional
+    weight sets the layer was packed with ('f16', 'split', 'wino'); amp / split: as passed to `conv2d`; guard: readable
+    floats around both inputs (tensors of this module carry GUARD); batch strides: default contiguous items;
+    addresses: overrides of the made-up operand addresses (in0, in1, residual, out) for alignment and overlap."""
+    kw = kh if kw is None else kw
+    if k_layout is None:
+        k_layout = (KLAYOUT_CHUNK32 if kh * kw > 1 and (c0 + c1) % 32 == 0 else KLAYOUT_TAP_MAJOR) | (KLAYOUT_Q4 if cout > 1 else 0)
+    oh, ow = (height + 2 * pad - kh) // stride + 1, (width + 2 * pad - kw) // stride + 1
+    at = dict(_PLAN_ADDRESSES, **(addresses or {}))
+    d = ConvDesc()
+    d.in0, d.in0_batch_stride = at['in0'], c0 * height * width if in0_batch_stride is None else in0_batch_stride
+    d.in1, d.in1_batch_stride = (at['in1'] if c1 else None), (c1 * height * width if in1_batch_stride is None else in1_batch_stride)
+    d.c0, d.c1, d.batch, d.height, d.width = c0, c1, batch, height, width
+    d.weight, d.bias = 5 << 40, None
+    d.cout, d.cout_pad, d.k_layout = cout, (cout + 31) // 32 * 32, k_layout
+    d.kh, d.kw, d.stride, d.pad, d.relu_in = kh, kw, stride, pad, 1 if relu_in else 0
+    d.residual = at['residual'] if residual else None
+    d.residual_batch_stride = (cout * oh * ow if residual_batch_stride is None else residual_batch_stride) if residual else 0
+    d.act, d.out = ACT_NONE, at['out']
+    d.in_guard_elems = guard
+    d.workspace, d.workspace_elems = (6 << 40 if workspace_elems else None), workspace_elems
+    d.split_scale_log2, d.split_flag = 0, None
+    if amp and 'f16' in weights:  # (the order of conv2d)
+        d.weight_f16, d.amp = 7 << 40, 1
+    elif split and 'split' in weights:
+        d.weight_f16, d.amp, d.split_flag = 7 << 40, 2, 8 << 40
+    else:
+        d.weight_f16, d.amp = None, 0
+    d.weight_wino = 9 << 40 if ('wino' in weights and d.amp == 0) else None
+    plan = ConvPlan()
+    check(lib().deva_conv2d_plan(d, plan), 'deva_conv2d_plan')
+
+    def info(l):
+        return ConvLaunchInfo(CONV_FAMILIES[l.family], (l.bm, l.bn), l.waves, l.wk, l.kind, bool(l.persistent), l.splits,
+                              l.per_split, l.group_m, (l.grid_x, l.grid_y), l.block)
+    return ConvPlanInfo(info(plan.first), info(plan.rerun) if plan.rerun.family else None, bool(plan.aliased), plan.sub_batch)
 
 
 # ------------------------------------------------------------------------------------------ pointwise
