@@ -646,6 +646,53 @@ int deva_mask_rle_write(int out_height, int out_width, int channels, const void*
                         int64_t scratch_bytes, const int32_t* n_host, int32_t* bounds,
                         int64_t capacity, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Detector output -> (index mask, segments): the tails of the reference's auto_segment
+ * (deva/ext/automatic_sam.py:93-145) and segment_with_text (deva/ext/grounding_dino.py:117-142).
+ *
+ * deva_detection_assemble: masks = n_masks binary planes [height][width], one byte per pixel with the
+ *   values 0 and 1 (a bool tensor's bytes), device memory.  P_k is plane k resized to the output size:
+ *   F.interpolate(mask_k.float(), (oh, ow), mode='bilinear'), align_corners=False, computed per pixel by
+ *   the sampling function of deva_index_mask (same coordinate, same roundings, no contraction); the
+ *   byte itself at equal sizes.  out is int64 [oh][ow]; records is int32 [n_masks][8] per mask, in the
+ *   order the masks were given:
+ *     0 id           the id the mask's segment takes, 0 if it takes none
+ *     1 mask_area    pixels the mask owns after the decision (policies below)
+ *     2 original_area  #(P_k > 0.5)
+ *     3 both         #(owned and P_k >= 0.5)
+ *     4 source_area  the mask's own pixel count at [height][width]
+ *     5 rank         position in id order: k, or the paint position for policy 2
+ *     6 score        the bits of scores[k] (fp32, device; 0 when scores is NULL): carried along so that one
+ *                    copy of this table is all the host needs
+ *     7 reserved, 0
+ *   policy 0, suppress small masks (automatic_sam.py:106-127): area_k = the fp32 sum of P_k (fixed
+ *     order: a repeated call and an identical plane give identical bits); hard = the first maximum over
+ *     {0.1, P_1*area_1, ..., P_n*area_n}, every term a rounded fp32 product; mask_area = #(hard == k).
+ *     Mask k is kept if mask_area, original_area and both are > 0 and not mask_area / original_area <
+ *     overlap_threshold, evaluated as torch evaluates an int64 / int64 true division against a Python
+ *     float: both counts to fp32, a correctly rounded fp32 division, the threshold rounded to fp32 (7
+ *     of 10 pixels pass a threshold of 0.7, which an fp64 evaluation would refuse).  Kept masks take ids
+ *     1, 2, ... in index order; out = that id where hard == k and P_k >= 0.5, else 0.
+ *   policy 1, prefer small masks (automatic_sam.py:128-143): the multiplier is 2*max(area) - area_k;
+ *     the masks with mask_area > 0 take ids 1, 2, ... in index order.  out = hard itself, i.e. k + 1,
+ *     NOT the id: the reference's mask keeps the uncompacted index while its segments_info is compacted,
+ *     and that is reproduced unless consistent_ids != 0, which writes the id (as policy 0 does).
+ *   policy 2, text-prompted (grounding_dino.py:124-140): masks are painted in descending source_area,
+ *     among equal areas the higher index first (np.flip of a stable ascending sort; numpy's default
+ *     argsort is only stable for short arrays, so for long lists the reference's own order among equal
+ *     areas is unspecified); a mask without a pixel P_k > 0.5 is skipped and takes no id, every other
+ *     one takes the next id in paint order and paints its P_k > 0.5 pixels over what is there.  A mask
+ *     that is painted over completely keeps its id (mask_area 0, id > 0).  both = mask_area here.
+ *   n_masks == 0 gives an all-zero mask and touches nothing else (automatic_sam.py:100-101).
+ *   At most 4096 masks; 2^31 pixels per plane.  scratch: deva_detection_scratch(...) bytes of device
+ *   memory, 16-byte aligned (-1: unsupported sizes).  Everything is checked before the first launch;
+ *   all work goes on `stream`, nothing synchronises. */
+int64_t deva_detection_scratch(int n_masks, int height, int width, int out_height, int out_width);
+int deva_detection_assemble(const uint8_t* masks, int n_masks, int height, int width, int out_height,
+                            int out_width, int policy, double overlap_threshold, int consistent_ids,
+                            const float* scores, void* scratch, int64_t scratch_bytes, int64_t* out,
+                            int32_t* records, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ wrapper in `ops.py` raises if handed a tensor that is not a contiguous fp32 HIP 
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libdeva_hip.so')
@@ -158,6 +158,9 @@ SIGNATURES = {
     'deva_mask_rle_scratch': (c_int64, [c_int, c_int, c_int]),
     'deva_mask_rle_count': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     'deva_mask_rle_write': (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    'deva_detection_scratch': (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    'deva_detection_assemble': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p,
+                                        c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 _LIB = None

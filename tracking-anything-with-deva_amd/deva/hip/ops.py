@@ -19,7 +19,7 @@ __all__ = ['PackedConv', 'pack_conv', 'conv2d', 'conv_plan', 'ConvLaunchInfo', '
            'affinity_topk', 'BankPrep', 'affinity_dense', 'dense_read', 'affinity_candidates', 'affinity_merge', 'usage_update', 'readout_sparse', 'bank_append', 'bank_gather_rows',
            'bank_export', 'rank', 'rank_select', 'evict_select', 'similarity_dense', 'softmax_columns',
            'label_histogram', 'merge_paint', 'lut_remap', 'index_mask', 'input_head',
-           'scores_u8', 'ensemble_index_mask', 'flip_w', 'frame_result', 'mask_rle', 'FrameProducts',
+           'scores_u8', 'ensemble_index_mask', 'flip_w', 'frame_result', 'mask_rle', 'FrameProducts', 'detection_assemble',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_SQUARE_PLUS_ONE']
 
 
@@ -1204,3 +1204,49 @@ def mask_rle(index: torch.Tensor, channels: Optional[int] = None) -> Tuple[torch
     check(lib().deva_mask_rle_write(oh, ow, c, scratch.data_ptr(), nbytes, n.data_ptr(),
                                     bounds.data_ptr() if total else None, total, _stream()), 'deva_mask_rle_write')
     return n, bounds
+
+
+# ------------------------------------------------------------------------------------------ detector output
+DETECTION_POLICIES = ('suppress_small', 'prefer_small', 'text')   # the policy numbers of deva_detection_assemble
+DETECTION_MAX_MASKS = 4096
+DETECTION_RECORD = ('id', 'mask_area', 'original_area', 'both', 'source_area', 'rank', 'score_bits', 'reserved')
+
+
+def detection_assemble(masks: torch.Tensor, size: Optional[Tuple[int, int]] = None, policy: str = 'suppress_small', *,
+                       scores: Optional[torch.Tensor] = None, overlap_threshold: float = 0.8,
+                       consistent_ids: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[N,H,W] binary masks of a detector (bool or uint8 holding 0 / 1; an fp32 {0,1} stack is converted once) ->
+    (int64 [OH,OW] index mask, int32 [N,8] records `DETECTION_RECORD`), both on the device: the assembly of the
+    reference's auto_segment (`policy` 'suppress_small' / 'prefer_small') and segment_with_text ('text'), contract in
+    include/deva_hip.h.  `scores` (fp32 [N], device) is carried into the records as bits.  Nothing synchronises."""
+    if policy not in DETECTION_POLICIES:
+        raise DevaHipError(f'detection_assemble: policy must be one of {DETECTION_POLICIES} (got {policy!r})')
+    if masks.dim() != 3:
+        raise DevaHipError(f'detection_assemble: [N,H,W] masks expected (got {tuple(masks.shape)})')
+    if masks.dtype not in (torch.bool, torch.uint8, torch.float32):
+        raise DevaHipError(f'detection_assemble: bool, uint8 or fp32 masks expected (got {masks.dtype})')
+    n, h, w = masks.shape
+    oh, ow = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if oh <= 0 or ow <= 0 or h <= 0 or w <= 0:
+        raise DevaHipError(f'detection_assemble: bad size {(h, w)} -> {(oh, ow)}')
+    if n > DETECTION_MAX_MASKS:
+        raise DevaHipError(f'detection_assemble: at most {DETECTION_MAX_MASKS} masks (got {n})')
+    if scores is not None and (scores.dtype != torch.float32 or tuple(scores.shape) != (n,)):
+        raise DevaHipError(f'detection_assemble: scores must be fp32 [{n}] (got {scores.dtype} {tuple(scores.shape)})')
+    require_hip(masks.device, 'detection_assemble: the masks')
+    nbytes = lib().deva_detection_scratch(n, h, w, oh, ow)
+    if nbytes < 0:
+        raise DevaHipError(f'detection_assemble: {n} masks of {h} x {w} to {oh} x {ow} is not supported')
+    if masks.dtype == torch.float32:
+        masks = masks != 0
+    masks = masks.contiguous()
+    planes = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+    out = torch.empty((oh, ow), dtype=torch.int64, device=masks.device)
+    records = torch.empty((n, len(DETECTION_RECORD)), dtype=torch.int32, device=masks.device)
+    scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=masks.device)
+    check(lib().deva_detection_assemble(_p(planes, torch.uint8, 'masks') if n else None, n, h, w, oh, ow,
+                                        DETECTION_POLICIES.index(policy), float(overlap_threshold), int(bool(consistent_ids)),
+                                        _p(scores, name='scores') if n else None,
+                                        scratch.data_ptr() if n else None, nbytes, _p(out, torch.int64), _p(records, torch.int32),
+                                        _stream()), 'deva_detection_assemble')
+    return out, records

@@ -1,0 +1,118 @@
+"""From a detector's output to what `DEVAInferenceCore.incorporate_detection` takes (not part of the reference's
+interface: the reference does this inside its detector wrappers, deva/ext/automatic_sam.py:93-145 and
+deva/ext/grounding_dino.py:117-142, which stay what `deva.ext` resolves to).
+
+A detector gives N binary instance masks and a score each.  The reference turns them into an index mask and a list of
+`ObjectInfo` with an N*H*W fp32 copy, two scaled copies, an argmax and a Python loop over the masks that synchronises
+several times per mask.  Here `ops.detection_assemble` does the arithmetic on the device in five launches; the host
+receives one small table (8 int32 per mask) and builds the list from it.
+
+Two quirks of the reference are reproduced on purpose (include/deva_hip.h has the contract):
+  * `assemble_automatic(..., suppress_small_objects=False)` returns a mask that holds the UNCOMPACTED index k + 1 of
+    mask k while `segments_info` is compacted to 1, 2, ...: with an empty mask in the list the two disagree, and
+    `incorporate_detection` then reads some segments from the wrong pixels (or none).  `consistent_ids=True` writes the
+    compacted id into the mask instead; it is off by default because the default is parity with the reference.
+  * `assemble_with_text` lists a mask that later, smaller masks painted over completely: its id is in
+    `segments_info` and absent from the mask.
+The text policy paints in descending area, among equal areas the higher index first: `np.flip` of a stable ascending
+sort.  numpy's default `argsort` is stable only for short arrays, so for long lists the reference's own order among
+equal areas is unspecified; this one is fixed.
+
+Choosing prompt points from a forward mask (automatic_sam.py:67-89) feeds the detector and stays with the caller;
+`estimate_forward_mask` gives the mask it needs."""
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from deva.hip import ops
+from deva.inference.object_info import ObjectInfo
+from deva.utils.tensor_utils import pad_divide_by, unpad
+
+
+def detection_size(h: int, w: int, min_side: int) -> Tuple[int, int]:
+    """the size the reference's detectors assemble at (automatic_sam.py:60-65): the shorter side scaled to `min_side`,
+    each side truncated (`int(h * scale)`); (h, w) itself for min_side <= 0"""
+    if min_side > 0:
+        scale = min_side / min(h, w)
+        return int(h * scale), int(w * scale)
+    return h, w
+
+
+def _records(masks: torch.Tensor, size, policy: str, scores, **kw):
+    """run the assembly and fetch its record table: one pinned, non-blocking copy and one event wait
+    -> (mask on the device, records as a list of rows, scores as floats)"""
+    device = masks.device
+    n = masks.shape[0]
+    on_device = torch.is_tensor(scores) and scores.device == device and scores.dtype == torch.float32
+    mask, records = ops.detection_assemble(masks, size, policy, scores=scores if on_device else None, **kw)
+    if n == 0:
+        return mask, [], []
+    if records.is_cuda:
+        host = torch.empty(records.shape, dtype=records.dtype, pin_memory=True)
+        host.copy_(records, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        event.synchronize()
+    else:
+        host = records
+    values = ([float(v) for v in host[:, 6].contiguous().view(torch.float32).tolist()] if on_device
+              else [v.item() if torch.is_tensor(v) else v for v in scores])
+    return mask, host.tolist(), values
+
+
+def _stack(masks) -> torch.Tensor:
+    if not torch.is_tensor(masks):
+        raise TypeError('masks: an [N,H,W] tensor on the device expected')
+    return masks
+
+
+def assemble_automatic(masks: torch.Tensor, scores, size: Optional[Tuple[int, int]] = None, *,
+                       suppress_small_objects: bool, overlap_threshold: float = 0.8,
+                       consistent_ids: bool = False) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+    """the tail of `auto_segment` (automatic_sam.py:93-145): `masks` [N,H,W] binary (bool / uint8 / fp32 {0,1}) and
+    `scores` [N] (the predicted IoUs: an fp32 tensor on the masks' device travels with the records, anything else is
+    read on the host) -> (int64 [OH,OW] index mask on the device, [ObjectInfo(id, score)]).
+    `suppress_small_objects=True`: large masks eat small ones, a mask that keeps less than `overlap_threshold`
+    (config['SAM_OVERLAP_THRESHOLD']) of its pixels is dropped.  False: small masks win; see the module docstring for
+    `consistent_ids`."""
+    masks = _stack(masks)
+    policy = 'suppress_small' if suppress_small_objects else 'prefer_small'
+    mask, rows, values = _records(masks, size, policy, scores, overlap_threshold=overlap_threshold,
+                                  consistent_ids=consistent_ids)
+    kept = sorted((r[0], k) for k, r in enumerate(rows) if r[0] > 0)
+    return mask, [ObjectInfo(id=i, score=values[k]) for i, k in kept]
+
+
+def assemble_with_text(masks: torch.Tensor, confidences: Sequence, class_ids: Sequence,
+                       size: Optional[Tuple[int, int]] = None) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+    """the tail of `segment_with_text` (grounding_dino.py:117-142): painter's order, largest mask first ->
+    (int64 [OH,OW] index mask on the device, [ObjectInfo(id, category_id, score)] in paint order)"""
+    masks = _stack(masks)
+    mask, rows, values = _records(masks, size, 'text', confidences)
+    classes = class_ids.tolist() if hasattr(class_ids, 'tolist') else list(class_ids)
+    kept = sorted((r[0], k) for k, r in enumerate(rows) if r[0] > 0)
+    return mask, [ObjectInfo(id=i, category_id=classes[k], score=values[k]) for i, k in kept]
+
+
+def estimate_forward_mask(core, image: torch.Tensor) -> torch.Tensor:
+    """the reference's `estimate_forward_mask` (deva/ext/automatic_processor.py:131-140): what the memory predicts for
+    the NEXT frame (`core.curr_ti + 1`), as an index mask of tmp ids at the frame's size.  The features and the key go
+    through the feature store, so the `step` / `incorporate_detection` of that frame finds them there.
+
+    Unlike the reference's, the call leaves no trace in the core: the reference lets this read update the sensory
+    memory and the usage counters a second time; here the read runs with `update_sensory=False` on a copy of the
+    counters, and the following `step` of the frame is bit-identical to a run without the call."""
+    padded, pad = pad_divide_by(image, 16)
+    batch = padded.unsqueeze(0)
+    ti = core.curr_ti + 1
+    store = core.image_feature_store
+    ms_features = store.get_ms_features(ti, batch)
+    key, _, selection = store.get_key(ti, batch)
+    saved_map, saved_usage = core._map16, core.memory.save_usage()
+    core._map16 = (padded.shape[-2] // 16, padded.shape[-1] // 16, image.device)
+    try:
+        prob = core._segment(key, selection, ms_features, update_sensory=False)
+    finally:
+        core._map16 = saved_map
+        core.memory.restore_usage(saved_usage)
+    return unpad(ops.index_mask(prob.contiguous()), pad)

@@ -276,6 +276,23 @@ class MemoryManager:
         if with_long:
             self.long_mem.apply_usage_fix(bucket_id, usage_fix, 0)
 
+    def save_usage(self) -> list:
+        """copies of every usage counter a read updates (working and long-term memory), for a read that must leave
+        no trace (`deva.inference.detections.estimate_forward_mask`); `restore_usage` puts them back"""
+        saved = []
+        for store in (self.work_mem, getattr(self, 'long_mem', None)):
+            if store is not None and store.save_usage:
+                for bucket_id in store.buckets:
+                    use, life = store.usage_arenas(bucket_id)
+                    saved.append((use, life, use.clone(), life.clone()))
+        return saved
+
+    @staticmethod
+    def restore_usage(saved: list) -> None:
+        for use, life, use_before, life_before in saved:
+            use.copy_(use_before)
+            life.copy_(life_before)
+
     def _read_bucket(self, bucket_id: int, bucket: List[int], qk, qe, rows: torch.Tensor) -> None:
         with_long, n_long, n_work = self._bucket_extent(bucket_id)
         usage_fix = self._usage_scratch(n_long + n_work, qk.device) if self.use_long_term else None
