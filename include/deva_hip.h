@@ -693,6 +693,74 @@ int deva_detection_assemble(const uint8_t* masks, int n_masks, int height, int w
                             const float* scores, void* scratch, int64_t scratch_bytes, int64_t* out,
                             int32_t* records, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Proposal filter: a promptable segmenter's mask logits and predicted IoUs, batch by batch -> the binary
+ * masks and scores that deva_detection_assemble takes.  The reference's generator does this in
+ * deva/ext/SAM/automatic_mask_generator.py:332-352 (per batch: IoU drop, stability drop, binarise, boxes)
+ * and automatic_mask_generator.py:272-278 (per image: box NMS).  The helpers it calls there come from
+ * segment_anything.utils.amg and torchvision.ops, which are neither part of the reference's tree nor
+ * needed here: the rules below ARE the contract, and the CPU statement (tests/emu_proposals.py) is written
+ * from them.
+ *
+ * A frame is: deva_proposal_begin, any number of deva_proposal_batch, deva_proposal_finish, one copy of
+ * `result` to the host, deva_proposal_gather.  All of it goes on `stream`; nothing synchronises.
+ *
+ * deva_proposal_batch: logits = batch planes [height][width] fp32, contiguous, device; iou_preds = fp32
+ *   [batch], device.  The thresholds are doubles, each rounded to fp32 once on the host:
+ *   t_iou = fp32(pred_iou_thresh), t_stab = fp32(stability_score_thresh), t_mask = fp32(mask_threshold),
+ *   t_hi = fp32(mask_threshold + stability_score_offset), t_lo = fp32(mask_threshold -
+ *   stability_score_offset), the sums formed in double.
+ *   1. Mask k is live iff iou_preds[k] > t_iou (automatic_mask_generator.py:333-335).  The `> 0.0` guard
+ *      of :333 is kept: with pred_iou_thresh <= 0 every mask is live, NaN predictions included.  A mask
+ *      that is not live is never read; the decision is taken on the device from iou_preds.
+ *   2. hi = #(x > t_hi), lo = #(x > t_lo) over the plane (strict; NaN compares false); stability =
+ *      fp32(hi) / fp32(lo), one correctly rounded fp32 division (:338-340).  The mask passes iff
+ *      stability >= t_stab (:341-343); lo = 0 gives NaN (0 / 0) and the mask is dropped.  The `> 0.0`
+ *      guard of :341 is kept: with stability_score_thresh <= 0 every live mask passes.  19 of 20 pixels
+ *      pass 0.95.
+ *   3. The planes of passing masks are stored as bytes 0 / 1 = (x > t_mask) (:346), in arrival order,
+ *      in `arena`: capacity planes of height*width bytes, caller-owned device memory, any alignment.
+ *   4. box = (x0, y0, x1, y1): the smallest and largest column and row of the set pixels, inclusive
+ *      pixel indices, int32 (:347); (0, 0, 0, 0) for an empty mask.
+ *   A passing mask beyond `capacity` is counted and not stored; nothing is written outside the arena.
+ *   Any batch >= 0; offsets into logits and the arena are 64-bit; a plane has at most 2^30 pixels.
+ * deva_proposal_finish: box NMS over the stored masks of the frame with the semantics of torchvision's
+ *   CPU kernel (:272-278):
+ *   5. boxes to fp32; area = (x1-x0)*(y1-y0), no +1 (a one-pixel-wide mask has area 0); inter =
+ *      max(0, min(x1)-max(x0)) * max(0, min(y1)-max(y0)); ovr = inter / (area_i + area_j - inter), every
+ *      operation a rounded fp32 one, no contraction; j is suppressed by a kept i that comes before it iff
+ *      (double)ovr > box_nms_thresh (NaN from 0 / 0 suppresses nothing).  The order is descending
+ *      iou_pred (a NaN prediction before every number, as torch sorts), among equal predictions the lower
+ *      arrival index first.  torchvision's order among ties is unspecified on the device; this one is
+ *      fixed.  The kept masks come out in that order: auto_segment depends on it (ids in order, first
+ *      maximum among ties).
+ *   result = int32 [4 + capacity*8], device: stored (= min(passed, capacity)), passed, kept, 0, then one
+ *   row per kept mask in keep order: arrival index, the bits of iou_pred, the bits of stability, x0, y0,
+ *   x1, y1, 0.  passed > capacity is the caller's overflow signal.
+ * deva_proposal_gather: out = the n_kept (the host's copy of result[2]) byte planes in keep order.
+ *   6. Crops are out of scope: the reference configures crop_n_layers = 0 only (automatic_sam.py:26-40),
+ *      where is_box_near_crop_edge (:350) cannot fire and the cross-crop NMS (:222-232) does not run.
+ *   7. postprocess_small_regions is out of scope (min_mask_region_area is never set; it needs OpenCV).
+ *   8. The choice of prompt points (automatic_sam.py:67-89) stays with the caller.
+ * deva_box_nms: rule 5 alone on boxes int32 [n_boxes][4] and scores fp32 [n_boxes] (device) -> keep int32
+ *   [n_boxes] (indices in keep order) and *n_keep, both device.
+ * At most 4096 stored masks / boxes (what deva_detection_assemble takes; one 64-bit suppression word per
+ * lane of a wave).  scratch: deva_proposal_scratch(capacity) bytes of device memory, 16-byte aligned (-1
+ * outside 1..4096), the same block from begin to gather; deva_box_nms asks for
+ * deva_proposal_scratch(n_boxes).  Everything is checked before the first launch. */
+int64_t deva_proposal_scratch(int capacity);
+int deva_proposal_begin(int capacity, void* scratch, int64_t scratch_bytes, void* stream);
+int deva_proposal_batch(const float* logits, const float* iou_preds, int batch, int height, int width,
+                        double pred_iou_thresh, double stability_score_thresh,
+                        double stability_score_offset, double mask_threshold, uint8_t* arena,
+                        int capacity, void* scratch, int64_t scratch_bytes, void* stream);
+int deva_proposal_finish(int capacity, double box_nms_thresh, void* scratch, int64_t scratch_bytes,
+                         int32_t* result, void* stream);
+int deva_proposal_gather(const uint8_t* arena, int capacity, int height, int width, const void* scratch,
+                         int64_t scratch_bytes, int n_kept, uint8_t* out, void* stream);
+int deva_box_nms(const int32_t* boxes, const float* scores, int n_boxes, double box_nms_thresh,
+                 void* scratch, int64_t scratch_bytes, int32_t* keep, int32_t* n_keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

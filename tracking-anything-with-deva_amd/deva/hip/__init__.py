@@ -161,6 +161,13 @@ SIGNATURES = {
     'deva_detection_scratch': (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     'deva_detection_assemble': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p,
                                         c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'deva_proposal_scratch': (c_int64, [c_int]),
+    'deva_proposal_begin': (c_int, [c_int, c_void_p, c_int64, c_void_p]),
+    'deva_proposal_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double,
+                                    c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    'deva_proposal_finish': (c_int, [c_int, c_double, c_void_p, c_int64, c_void_p, c_void_p]),
+    'deva_proposal_gather': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    'deva_box_nms': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 _LIB = None

@@ -20,6 +20,7 @@ __all__ = ['PackedConv', 'pack_conv', 'conv2d', 'conv_plan', 'ConvLaunchInfo', '
            'bank_export', 'rank', 'rank_select', 'evict_select', 'similarity_dense', 'softmax_columns',
            'label_histogram', 'merge_paint', 'lut_remap', 'index_mask', 'input_head',
            'scores_u8', 'ensemble_index_mask', 'flip_w', 'frame_result', 'mask_rle', 'FrameProducts', 'detection_assemble',
+           'ProposalState', 'ProposalResult', 'proposal_state', 'proposal_begin', 'proposal_batch', 'proposal_finish', 'box_nms',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_SQUARE_PLUS_ONE']
 
 
@@ -1250,3 +1251,119 @@ def detection_assemble(masks: torch.Tensor, size: Optional[Tuple[int, int]] = No
                                         scratch.data_ptr() if n else None, nbytes, _p(out, torch.int64), _p(records, torch.int32),
                                         _stream()), 'deva_detection_assemble')
     return out, records
+
+
+# ------------------------------------------------------------------------------------------ proposal filter
+PROPOSAL_MAX_MASKS = 4096
+PROPOSAL_ROW = ('index', 'iou_pred_bits', 'stability_bits', 'x0', 'y0', 'x1', 'y1', 'reserved')   # a row of the result table
+
+
+class ProposalResult(NamedTuple):
+    """what survived a frame, in keep order (descending predicted IoU, among equal ones the earlier arrival)"""
+    masks: torch.Tensor       # uint8 [K,H,W] 0 / 1, device
+    iou_preds: torch.Tensor   # fp32 [K], device
+    stability: torch.Tensor   # fp32 [K], device
+    boxes: torch.Tensor       # int32 [K,4] x0, y0, x1, y1 (inclusive pixel indices), host
+    index: torch.Tensor       # int32 [K] arrival index among the frame's stored masks, host
+
+
+@dataclass
+class ProposalState:
+    """device memory of one proposal filter: the arena of byte planes, the scratch, the result table and its pinned copy"""
+    height: int
+    width: int
+    capacity: int
+    arena: torch.Tensor
+    scratch: torch.Tensor
+    scratch_bytes: int
+    result: torch.Tensor
+    host: torch.Tensor
+
+
+def proposal_state(height: int, width: int, capacity: int, device, arena: Optional[torch.Tensor] = None) -> ProposalState:
+    """allocate (once; `proposal_begin` starts every frame on it) the memory of a filter for `capacity` stored masks of
+    height x width: capacity*height*width bytes of arena (or the caller's own contiguous uint8 tensor of that many
+    elements), under 2.3 MB of scratch and 128 KB of result table at the largest capacity"""
+    height, width, capacity = int(height), int(width), int(capacity)
+    if height <= 0 or width <= 0 or height * width > 1 << 30:
+        raise DevaHipError(f'proposal_state: bad plane size {(height, width)}')
+    if not 1 <= capacity <= PROPOSAL_MAX_MASKS:
+        raise DevaHipError(f'proposal_state: a capacity of 1 to {PROPOSAL_MAX_MASKS} masks (got {capacity})')
+    require_hip(device, 'proposal_state: the filter')
+    if arena is None:
+        arena = torch.empty((capacity, height, width), dtype=torch.uint8, device=device)
+    elif arena.dtype != torch.uint8 or arena.numel() != capacity * height * width or not arena.is_contiguous():
+        raise DevaHipError(f'proposal_state: the arena must be a contiguous uint8 tensor of {capacity} x {height} x {width}')
+    _p(arena, torch.uint8, 'arena')
+    nbytes = lib().deva_proposal_scratch(capacity)
+    scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=device)
+    result = torch.empty(4 + capacity * len(PROPOSAL_ROW), dtype=torch.int32, device=device)
+    host = torch.empty(result.shape, dtype=torch.int32, pin_memory=True)
+    return ProposalState(height, width, capacity, arena, scratch, nbytes, result, host)
+
+
+def proposal_begin(state: ProposalState) -> None:
+    """start a frame: nothing stored, nothing counted"""
+    check(lib().deva_proposal_begin(state.capacity, state.scratch.data_ptr(), state.scratch_bytes, _stream()),
+          'deva_proposal_begin')
+
+
+def proposal_batch(state: ProposalState, logits: torch.Tensor, iou_preds: torch.Tensor, *, pred_iou_thresh: float,
+                   stability_score_thresh: float, stability_score_offset: float, mask_threshold: float) -> None:
+    """one batch of a segmenter: `logits` fp32 [B,H,W] and `iou_preds` fp32 [B] on the device.  The masks that pass the
+    IoU and the stability drop (include/deva_hip.h, deva_proposal_batch) are stored in the arena as bytes.  Three
+    launches, nothing synchronises; B = 0 is fine."""
+    if logits.dim() != 3 or tuple(logits.shape[1:]) != (state.height, state.width):
+        raise DevaHipError(f'proposal_batch: [B,{state.height},{state.width}] logits expected (got {tuple(logits.shape)})')
+    b = logits.shape[0]
+    if tuple(iou_preds.shape) != (b,):
+        raise DevaHipError(f'proposal_batch: iou_preds must be fp32 [{b}] (got {tuple(iou_preds.shape)})')
+    check(lib().deva_proposal_batch(_p(logits, name='logits') if b else None, _p(iou_preds, name='iou_preds') if b else None,
+                                    b, state.height, state.width, float(pred_iou_thresh), float(stability_score_thresh),
+                                    float(stability_score_offset), float(mask_threshold), state.arena.data_ptr(),
+                                    state.capacity, state.scratch.data_ptr(), state.scratch_bytes, _stream()),
+          'deva_proposal_batch')
+
+
+def proposal_finish(state: ProposalState, box_nms_thresh: float) -> ProposalResult:
+    """end a frame: box NMS over what was stored, ONE pinned copy of the result table (the only synchronisation of the
+    frame), then the kept planes gathered in keep order.  Raises if more masks passed than the arena holds."""
+    check(lib().deva_proposal_finish(state.capacity, float(box_nms_thresh), state.scratch.data_ptr(), state.scratch_bytes,
+                                     state.result.data_ptr(), _stream()), 'deva_proposal_finish')
+    state.host.copy_(state.result, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+    event.synchronize()
+    stored, passed, kept = state.host[:3].tolist()
+    if passed > state.capacity:
+        raise DevaHipError(f'proposal_finish: {passed} masks passed the filter, the arena holds {state.capacity}: '
+                           'none beyond it was stored (raise `capacity`, at most 4096, or the thresholds)')
+    cols = len(PROPOSAL_ROW)
+    rows = state.host[4:4 + kept * cols].view(kept, cols).clone()
+    on_device = state.result[4:4 + kept * cols].view(kept, cols)
+    masks = torch.empty((kept, state.height, state.width), dtype=torch.uint8, device=state.arena.device)
+    check(lib().deva_proposal_gather(state.arena.data_ptr(), state.capacity, state.height, state.width,
+                                     state.scratch.data_ptr(), state.scratch_bytes, kept, masks.data_ptr() if kept else None,
+                                     _stream()), 'deva_proposal_gather')
+    return ProposalResult(masks, on_device[:, 1].contiguous().view(torch.float32),
+                          on_device[:, 2].contiguous().view(torch.float32), rows[:, 3:7].contiguous(), rows[:, 0].contiguous())
+
+
+def box_nms(boxes: torch.Tensor, scores: torch.Tensor, box_nms_thresh: float) -> torch.Tensor:
+    """int32 [M,4] boxes (x0, y0, x1, y1) and fp32 [M] scores on the device -> int32 [K] kept indices on the device, in
+    keep order: rule 5 of the proposal filter's contract (torchvision's CPU arithmetic; descending score, among equal
+    scores the lower index).  Reading K synchronises once."""
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise DevaHipError(f'box_nms: int32 [M,4] boxes expected (got {tuple(boxes.shape)})')
+    m = boxes.shape[0]
+    if tuple(scores.shape) != (m,):
+        raise DevaHipError(f'box_nms: scores must be fp32 [{m}] (got {tuple(scores.shape)})')
+    if m > PROPOSAL_MAX_MASKS:
+        raise DevaHipError(f'box_nms: at most {PROPOSAL_MAX_MASKS} boxes (got {m})')
+    bp, sp = _p(boxes, torch.int32, 'boxes'), _p(scores, name='scores')
+    keep = torch.empty(m + 1, dtype=torch.int32, device=boxes.device)     # the count travels behind the list
+    nbytes = lib().deva_proposal_scratch(m) if m else 0
+    scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=boxes.device)
+    check(lib().deva_box_nms(bp if m else None, sp if m else None, m, float(box_nms_thresh), scratch.data_ptr() if m else None,
+                             nbytes, keep.data_ptr(), keep.data_ptr() + 4 * m, _stream()), 'deva_box_nms')
+    return keep[:int(keep[m])].clone()

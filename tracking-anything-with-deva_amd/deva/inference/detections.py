@@ -19,7 +19,8 @@ sort.  numpy's default `argsort` is stable only for short arrays, so for long li
 equal areas is unspecified; this one is fixed.
 
 Choosing prompt points from a forward mask (automatic_sam.py:67-89) feeds the detector and stays with the caller;
-`estimate_forward_mask` gives the mask it needs."""
+`estimate_forward_mask` gives the mask it needs.  The masks and scores of `assemble_automatic` come out of
+`deva.inference.proposals.ProposalFilter`, which filters a promptable segmenter's raw logits on the device."""
 from typing import List, Optional, Sequence, Tuple
 
 import torch
