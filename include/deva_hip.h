@@ -741,7 +741,7 @@ int deva_detection_assemble(const uint8_t* masks, int n_masks, int height, int w
  *   6. Crops are out of scope: the reference configures crop_n_layers = 0 only (automatic_sam.py:26-40),
  *      where is_box_near_crop_edge (:350) cannot fire and the cross-crop NMS (:222-232) does not run.
  *   7. postprocess_small_regions is out of scope (min_mask_region_area is never set; it needs OpenCV).
- *   8. The choice of prompt points (automatic_sam.py:67-89) stays with the caller.
+ *   8. The choice of prompt points (automatic_sam.py:67-89) is deva_prompt_points, below.
  * deva_box_nms: rule 5 alone on boxes int32 [n_boxes][4] and scores fp32 [n_boxes] (device) -> keep int32
  *   [n_boxes] (indices in keep order) and *n_keep, both device.
  * At most 4096 stored masks / boxes (what deva_detection_assemble takes; one 64-bit suppression word per
@@ -760,6 +760,54 @@ int deva_proposal_gather(const uint8_t* arena, int capacity, int height, int wid
                          int64_t scratch_bytes, int n_kept, uint8_t* out, void* stream);
 int deva_box_nms(const int32_t* boxes, const float* scores, int n_boxes, double box_nms_thresh,
                  void* scratch, int64_t scratch_bytes, int32_t* keep, int32_t* n_keep, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Prompt points of an automatic detection frame: the tracker's forward mask -> the grid points that lie on
+ * background, the only ones the segmenter is asked about (the reference: deva/ext/automatic_sam.py:67-89,
+ * about fifteen ATen launches, a boolean-index copy and a .cpu()).  The rules below ARE the contract; the
+ * CPU statement (tests/emu_prompts.py) is written from them and the device agrees with it bit for bit.
+ *
+ * deva_prompt_points:
+ *   1. Mask (automatic_sam.py:69).  mask = height x width index mask, contiguous, device; mask_elem_bytes =
+ *      8 (int64: what estimate_forward_mask returns; compared as a signed 64-bit value, an id of 2^31 + 5
+ *      is foreground and -3 is not) or 1 (uint8).  Foreground is mask > 0, taken as 1.0f or 0.0f.
+ *   2. Low-resolution map (automatic_sam.py:70-73).  low = [height / 16][width / 16], integer division:
+ *      the separable antialiased triangle filter of F.interpolate(mode='bilinear', antialias=True) with
+ *      scale = 16.0f EXACTLY on both axes -- the scale_factor the reference passes, not height / low_h
+ *      (the two differ whenever a side is no multiple of 16, and the maps then differ by up to 0.33).
+ *      Support 16: the window of output o is the positions 16 o - 8 ... 16 o + 23, clipped to the axis
+ *      (at most 32 taps); the weight of position p is max(0, 1 - |p - (16 o + 8) + 0.5| / 16), divided by
+ *      the sum of the window's weights (one correctly rounded fp32 division per tap).  Columns before
+ *      rows: rows[y][ox] = the sum along the row, then low[oy][ox] = the sum of rows[.][ox] down the
+ *      column; each sum starts at 0.0f and adds value * weight in tap order, the product and the sum
+ *      each rounded to fp32 (no contraction).  height < 16 or width < 16 is an argument error (torch
+ *      raises there too); a side is at most 65536 and the mask has at most 2^30 pixels.
+ *   3. Points (automatic_sam.py:74-79, 81).  points_xy = fp32 [points][2], device: normalised (x, y),
+ *      1 <= points <= 16384.  The grid is the caller's: the reference's torch.linspace values pass through
+ *      bit for bit, and so does an explicit point grid.
+ *   4. Label (automatic_sam.py:80).  The bilinear sample of low with the arithmetic of
+ *      F.grid_sample(align_corners=False, padding_mode='zeros'), every operation a rounded fp32 one:
+ *        g = x * 2 - 1;  ix = ((g + 1) * low_w - 1) / 2;  likewise iy from y and low_h;
+ *        x0 = floor(ix), x1 = x0 + 1, y0 = floor(iy), y1 = y0 + 1;
+ *        nw = low[y0][x0] * ((x1 - ix) * (y1 - iy));   ne = low[y0][x1] * ((ix - x0) * (y1 - iy));
+ *        sw = low[y1][x0] * ((x1 - ix) * (iy - y0));   se = low[y1][x1] * ((ix - x0) * (iy - y0));
+ *        label = ((nw + ne) + sw) + se.
+ *      A tap outside low is 0.0f in that sum (the outermost points of a dense grid do reach outside); a
+ *      coordinate that is not finite has no tap inside.
+ *   5. Kept set (automatic_sam.py:82).  A point is kept iff label < fp32(threshold): strict, in fp32 (the
+ *      reference's threshold is 0.01; a NaN label is not kept).  The kept points, the bits of their input
+ *      rows, go to out_points fp32 [points][2] in input order; rows beyond the count are left untouched.
+ *      out_count[0] = their number (0 is a valid result: automatic_sam.py:83-86), out_labels fp32 [points]
+ *      = every label.  The order never depends on the order of atomics: there are none.
+ *   6. Execution.  Three launches on `stream`, nothing synchronises; scratch = deva_prompt_scratch(height,
+ *      width, points) bytes of the caller's device memory, 16-byte aligned (-1 for a size or a number of
+ *      points outside the ranges above; host only).  mask and the outputs are aligned to their elements.
+ *      Everything is checked before the first launch.  Negative points are out of scope
+ *      (automatic_sam.py:87-88 sets them to None). */
+int64_t deva_prompt_scratch(int height, int width, int points);
+int deva_prompt_points(const void* mask, int mask_elem_bytes, int height, int width, const float* points_xy,
+                       int points, double threshold, void* scratch, int64_t scratch_bytes, float* out_points,
+                       float* out_labels, int32_t* out_count, void* stream);
 
 #ifdef __cplusplus
 }

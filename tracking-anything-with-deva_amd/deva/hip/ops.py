@@ -21,6 +21,7 @@ __all__ = ['PackedConv', 'pack_conv', 'conv2d', 'conv_plan', 'ConvLaunchInfo', '
            'label_histogram', 'merge_paint', 'lut_remap', 'index_mask', 'input_head',
            'scores_u8', 'ensemble_index_mask', 'flip_w', 'frame_result', 'mask_rle', 'FrameProducts', 'detection_assemble',
            'ProposalState', 'ProposalResult', 'proposal_state', 'proposal_begin', 'proposal_batch', 'proposal_finish', 'box_nms',
+           'prompt_points', 'PROMPT_MAX_POINTS',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_SQUARE_PLUS_ONE']
 
 
@@ -1367,3 +1368,56 @@ def box_nms(boxes: torch.Tensor, scores: torch.Tensor, box_nms_thresh: float) ->
     check(lib().deva_box_nms(bp if m else None, sp if m else None, m, float(box_nms_thresh), scratch.data_ptr() if m else None,
                              nbytes, keep.data_ptr(), keep.data_ptr() + 4 * m, _stream()), 'deva_box_nms')
     return keep[:int(keep[m])].clone()
+
+
+# ------------------------------------------------------------------------------------------ prompt points
+PROMPT_MAX_POINTS = 16384
+PROMPT_MIN_SIDE = 16   # the map is [H / 16, W / 16]
+
+
+def prompt_points(mask: torch.Tensor, points_xy: torch.Tensor, threshold: float = 0.01, *,
+                  scratch: Optional[torch.Tensor] = None,
+                  packed: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """[H,W] index mask (int64, uint8 or bool; foreground is `> 0`) and fp32 [P,2] normalised (x, y) points, both on the
+    device -> (points fp32 [P,2], labels fp32 [P], count int32 [1]) on the device: the choice of prompt points of the
+    reference's auto_segment (automatic_sam.py:67-89; contract in include/deva_hip.h, deva_prompt_points).  The first
+    `count` rows of `points` are the points whose label, the bilinear sample of the 16x antialiased foreground map, is
+    below `threshold`, in input order; the rows beyond are not written.  Three launches, nothing synchronises.
+    `scratch`: the caller's int32 device tensor of at least deva_prompt_scratch bytes (default: allocated here).
+    `packed`: the caller's fp32 [2 P + 1] device tensor that receives the points and, behind them, the count (one
+    host copy then fetches both); `points` and `count` are views of it."""
+    if mask.dim() != 2:
+        raise DevaHipError(f'prompt_points: an [H,W] mask expected (got {tuple(mask.shape)})')
+    if mask.dtype not in (torch.int64, torch.uint8, torch.bool):
+        raise DevaHipError(f'prompt_points: an int64, uint8 or bool mask expected (got {mask.dtype})')
+    h, w = mask.shape
+    if h < PROMPT_MIN_SIDE or w < PROMPT_MIN_SIDE:
+        raise DevaHipError(f'prompt_points: a mask of at least {PROMPT_MIN_SIDE} x {PROMPT_MIN_SIDE} (got {h} x {w})')
+    if points_xy.dim() != 2 or points_xy.shape[1] != 2:
+        raise DevaHipError(f'prompt_points: fp32 [P,2] points expected (got {tuple(points_xy.shape)})')
+    n = points_xy.shape[0]
+    if not 1 <= n <= PROMPT_MAX_POINTS:
+        raise DevaHipError(f'prompt_points: 1 to {PROMPT_MAX_POINTS} points (got {n})')
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise DevaHipError('prompt_points: the threshold is not a number')
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    mp, pp = _p(mask, mask.dtype, 'mask'), _p(points_xy, name='points_xy')
+    device = mask.device
+    nbytes = lib().deva_prompt_scratch(h, w, n)
+    if nbytes < 0:
+        raise DevaHipError(f'prompt_points: a mask of {h} x {w} with {n} points is not supported')
+    if scratch is None:
+        scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=device)
+    elif _p(scratch, torch.int32, 'scratch') % 16 or scratch.numel() * 4 < nbytes:
+        raise DevaHipError(f'prompt_points: the scratch must be a 16-byte aligned int32 tensor of {nbytes} bytes')
+    if packed is None:
+        packed = torch.empty(2 * n + 1, dtype=torch.float32, device=device)
+    elif _p(packed, name='packed') is None or packed.numel() != 2 * n + 1:
+        raise DevaHipError(f'prompt_points: `packed` must be fp32 [{2 * n + 1}]')
+    labels = torch.empty(n, dtype=torch.float32, device=device)
+    check(lib().deva_prompt_points(mp, mask.element_size(), h, w, pp, n, threshold, scratch.data_ptr(), nbytes,
+                                   packed.data_ptr(), labels.data_ptr(), packed.data_ptr() + 8 * n, _stream()),
+          'deva_prompt_points')
+    return packed[:2 * n].view(n, 2), labels, packed[2 * n:].view(torch.int32)

@@ -1,0 +1,159 @@
+"""The reference's automatic frame loop on this package's pieces (not part of the reference's interface: the reference
+runs it as deva/ext/automatic_processor.py:28-128 `process_frame_automatic` with deva/ext/automatic_sam.py `auto_segment`
+and demo_utils.py `flush_buffer`, modules that import OpenCV and segment_anything when they load).
+
+    processor = AutomaticProcessor(core, segmenter, saver=FrameResultSaver(...))
+    for ti, (name, image_np) in enumerate(frames):        # RGB uint8 H*W*3
+        processor.process_frame(image_np, ti, name)
+    processor.flush()
+
+A detection frame is: `estimate_forward_mask` (once the memory is engaged) -> `forward_prompt_points` (the grid points on
+background: one copy of 8 bytes per point) -> the segmenter, batch by batch -> `ProposalFilter` (one copy of the result
+table) -> `assemble_automatic` -> `incorporate_detection(..., incremental=True)`; the other frames are `step`.
+
+The segmenter is any object with
+    set_image(image_np)                  the frame, RGB uint8 H*W*3 (numpy)
+    predict_points(points_px)            fp32 [B,2] pixel (x, y) on the device -> (logits fp32 [B*M,H,W] contiguous at the
+                                         frame's own size, iou_preds fp32 [B*M]), both on the device
+    reset_image()                        optional
+    mask_threshold                       optional attribute (default 0.0, SAM's)
+INTEGRATION.md wraps a `SamPredictor` this way."""
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from deva.inference import detections
+from deva.inference.object_info import ObjectInfo
+from deva.inference.proposals import ProposalFilter
+from deva.utils.tensor_utils import frame_to_network_input
+
+__all__ = ['AutomaticProcessor', 'BufferedFrame', 'CONFIG_KEYS']
+
+CONFIG_KEYS = ('size', 'suppress_small_objects', 'temporal_setting', 'num_voting_frames', 'detection_every',
+               'SAM_NUM_POINTS_PER_SIDE', 'SAM_NUM_POINTS_PER_BATCH', 'SAM_PRED_IOU_THRESHOLD', 'SAM_OVERLAP_THRESHOLD')
+
+
+class BufferedFrame:
+    """what the semi-online buffer holds: the fields of the reference's FrameInfo (frame_utils.py:7-30) that
+    `vote_in_temporary_buffer` and `clear_buffer` read, plus the decoded frame for the saver's overlay"""
+
+    def __init__(self, image: torch.Tensor, mask: Optional[torch.Tensor], segments_info: Optional[List[ObjectInfo]], ti: int,
+                 info: Dict, image_np: Optional[np.ndarray] = None):
+        self.image, self.mask, self.segments_info, self.ti, self.info, self.image_np = image, mask, segments_info, ti, info, image_np
+
+    name = property(lambda self: self.info['frame'][0])
+    shape = property(lambda self: self.info['shape'])
+
+
+class AutomaticProcessor:
+    """`process_frame_automatic` and `flush_buffer` of the reference's demo as one object around a `DEVAInferenceCore`.
+
+    The configuration is `core.config`; every key of `CONFIG_KEYS` must be there (a missing one raises KeyError with its
+    name: no default is invented).  `capacity` is the `ProposalFilter`'s (masks that may pass the drops in one frame).
+    `saver`: anything with `save_mask(prob, frame_name, need_resize=, shape=, image_np=)`, e.g. `FrameResultSaver`.
+    `next_voting_frame` starts at num_voting_frames - 1, as the demo sets it."""
+
+    def __init__(self, core, segmenter, *, capacity: int = 512, saver=None):
+        self.core, self.segmenter, self.capacity, self.saver = core, segmenter, int(capacity), saver
+        for key in CONFIG_KEYS:
+            if key not in core.config:
+                raise KeyError(key)
+        if core.config['temporal_setting'] not in ('online', 'semionline'):
+            raise ValueError(f"temporal_setting must be 'online' or 'semionline' (got {core.config['temporal_setting']!r})")
+        self.next_voting_frame = core.config['num_voting_frames'] - 1
+        self._filter = None
+
+    # ------------------------------------------------------------------ auto_segment
+    def _proposal_filter(self, h: int, w: int) -> ProposalFilter:
+        flt = self._filter
+        if flt is None or (flt.height, flt.width) != (h, w):   # once per processor, again when the frame size changes
+            flt = self._filter = ProposalFilter(h, w, capacity=self.capacity,
+                                                pred_iou_thresh=self.core.config['SAM_PRED_IOU_THRESHOLD'],
+                                                mask_threshold=getattr(self.segmenter, 'mask_threshold', 0.0))
+        return flt
+
+    def segment(self, image_np: np.ndarray, forward_mask: Optional[torch.Tensor],
+                device=None) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+        """`auto_segment` (automatic_sam.py:47-145): the frame and the tracker's forward mask (None: the whole grid is
+        asked) -> (int64 index mask at `detection_size`, on the device; [ObjectInfo(id, score)])"""
+        cfg = self.core.config
+        h, w = image_np.shape[:2]
+        size = detections.detection_size(h, w, cfg['size'])
+        n = cfg['SAM_NUM_POINTS_PER_SIDE']
+        if forward_mask is not None:
+            device = forward_mask.device
+            points = detections.forward_prompt_points(forward_mask, n)
+        else:
+            device = torch.device('cuda') if device is None else device
+            points = detections.prompt_grid(n, 'cpu').numpy()
+        if len(points) == 0:          # everything is tracked: the segmenter is not asked (automatic_sam.py:83-86)
+            return torch.zeros(size, dtype=torch.int64, device=device), []
+        self.segmenter.set_image(image_np)
+        # pixel coordinates as the generator forms them (automatic_mask_generator.py:253-257): fp32 points times the
+        # integer (w, h), in double; the segmenter takes fp32
+        points_px = torch.from_numpy((points * np.array([w, h])[None, :]).astype(np.float32)).to(device)
+        flt = self._proposal_filter(h, w)
+        flt.reset()
+        per_batch = int(cfg['SAM_NUM_POINTS_PER_BATCH'])
+        for first in range(0, points_px.shape[0], per_batch):
+            logits, iou_preds = self.segmenter.predict_points(points_px[first:first + per_batch])
+            flt.add(logits, iou_preds)
+        if hasattr(self.segmenter, 'reset_image'):
+            self.segmenter.reset_image()
+        found = flt.finish()
+        return detections.assemble_automatic(found.masks, found.iou_preds, size,
+                                             suppress_small_objects=cfg['suppress_small_objects'],
+                                             overlap_threshold=cfg['SAM_OVERLAP_THRESHOLD'])
+
+    # ------------------------------------------------------------------ process_frame_automatic
+    def _emit(self, produced: List, prob: torch.Tensor, frame_name: str, image_np: np.ndarray) -> None:
+        produced.append((frame_name, prob))
+        if self.saver is not None:
+            h, w = image_np.shape[:2]
+            self.saver.save_mask(prob, frame_name, need_resize=self.core.config['size'] > 0, shape=(h, w), image_np=image_np)
+
+    def _detect(self, image: torch.Tensor, image_np: np.ndarray) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+        forward_mask = detections.estimate_forward_mask(self.core, image) if self.core.memory.engaged else None
+        return self.segment(image_np, forward_mask, device=image.device)
+
+    def process_frame(self, image_np: np.ndarray, ti: int, frame_name: str) -> List[Tuple[str, torch.Tensor]]:
+        """one frame of the video (RGB uint8 H*W*3) -> the (frame name, probabilities) pairs this call produced: one in
+        the online setting; none, one or a voting window's worth in the semi-online one"""
+        core, cfg = self.core, self.core.config
+        h, w = image_np.shape[:2]
+        image = frame_to_network_input(image_np, cfg['size'], antialias=False)   # the demo's rule (demo_utils.py:10-19)
+        produced: List[Tuple[str, torch.Tensor]] = []
+        if cfg['temporal_setting'] == 'semionline':
+            if ti + cfg['num_voting_frames'] > self.next_voting_frame:
+                mask, segments_info = self._detect(image, image_np)
+                info = {'frame': [frame_name], 'shape': [h, w]}
+                core.add_to_temporary_buffer(BufferedFrame(image, mask, segments_info, ti, info, image_np))   # wait for more
+                if ti == self.next_voting_frame:
+                    first = core.frame_buffer[0]
+                    _, mask, new_segments_info = core.vote_in_temporary_buffer(keyframe_selection='first')
+                    prob = core.incorporate_detection(first.image, mask, new_segments_info, incremental=True)
+                    self.next_voting_frame += cfg['detection_every']
+                    self._emit(produced, prob, first.name, first.image_np)
+                    for frame in core.frame_buffer[1:]:
+                        self._emit(produced, core.step(frame.image, None, None), frame.name, frame.image_np)
+                    core.clear_buffer()
+            else:
+                self._emit(produced, core.step(image, None, None), frame_name, image_np)    # standard propagation
+        elif cfg['temporal_setting'] == 'online':
+            if ti % cfg['detection_every'] == 0:
+                mask, segments_info = self._detect(image, image_np)
+                prob = core.incorporate_detection(image, mask, segments_info, incremental=True)
+            else:
+                prob = core.step(image, None, None)
+            self._emit(produced, prob, frame_name, image_np)
+        else:
+            raise ValueError(f"temporal_setting must be 'online' or 'semionline' (got {cfg['temporal_setting']!r})")
+        return produced
+
+    def flush(self) -> List[Tuple[str, torch.Tensor]]:
+        """`flush_buffer` (demo_utils.py:22-46): step the frames that are still buffered when the video ends"""
+        produced: List[Tuple[str, torch.Tensor]] = []
+        for frame in self.core.frame_buffer:
+            self._emit(produced, self.core.step(frame.image, None, None), frame.name, frame.image_np)
+        return produced

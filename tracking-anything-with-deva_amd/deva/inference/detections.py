@@ -18,11 +18,14 @@ The text policy paints in descending area, among equal areas the higher index fi
 sort.  numpy's default `argsort` is stable only for short arrays, so for long lists the reference's own order among
 equal areas is unspecified; this one is fixed.
 
-Choosing prompt points from a forward mask (automatic_sam.py:67-89) feeds the detector and stays with the caller;
-`estimate_forward_mask` gives the mask it needs.  The masks and scores of `assemble_automatic` come out of
-`deva.inference.proposals.ProposalFilter`, which filters a promptable segmenter's raw logits on the device."""
+Choosing prompt points from a forward mask (automatic_sam.py:67-89) feeds the detector: `forward_prompt_points` does
+it on the device (`ops.prompt_points`: three launches and one copy of 8 bytes per point) from the mask that
+`estimate_forward_mask` gives.  The masks and scores of `assemble_automatic` come out of
+`deva.inference.proposals.ProposalFilter`, which filters a promptable segmenter's raw logits on the device;
+`deva.inference.automatic.AutomaticProcessor` ties all of it into the reference's frame loop."""
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from deva.hip import ops
@@ -117,3 +120,50 @@ def estimate_forward_mask(core, image: torch.Tensor) -> torch.Tensor:
         core._map16 = saved_map
         core.memory.restore_usage(saved_usage)
     return unpad(ops.index_mask(prob.contiguous()), pad)
+
+
+_GRIDS = {}
+_PINNED = {}
+
+
+def prompt_grid(n_per_side: int, device) -> torch.Tensor:
+    """the prompt grid of automatic_sam.py:74-81 as fp32 [n*n,2] normalised (x, y) on `device`: n values from
+    1 / (2 n) to 1 - 1 / (2 n) per axis, x fastest.  `torch.linspace` runs on the CPU, so the values are the ones a
+    CPU run of the reference samples at, and the upload happens once per (n, device)."""
+    n = int(n_per_side)
+    if n < 1:
+        raise ValueError(f'prompt_grid: at least one point per side (got {n_per_side})')
+    key = (n, str(torch.device(device)))
+    if key not in _GRIDS:
+        offset = 1 / (2 * n)
+        side = torch.linspace(offset, 1 - offset, n)
+        grid = torch.stack([side.unsqueeze(0).repeat(n, 1), side.unsqueeze(1).repeat(1, n)], dim=-1).view(-1, 2)
+        _GRIDS[key] = grid.contiguous().to(device)
+    return _GRIDS[key]
+
+
+def forward_prompt_points(forward_mask: torch.Tensor, n_per_side: Optional[int] = None, *,
+                          point_grid: Optional[torch.Tensor] = None, threshold: float = 0.01) -> np.ndarray:
+    """automatic_sam.py:67-82: the points of the grid (`prompt_grid(n_per_side)`, or `point_grid`: fp32 [P,2] normalised
+    (x, y)) at which the forward mask, blurred to 1/16 of its size, is below `threshold` -> host fp32 [K,2] in grid
+    order, what the reference hands to `generate(image, positive_points, None)`.  K = 0 is a valid result.  The host
+    pays one pinned, non-blocking copy of 8 P + 4 bytes and one event wait."""
+    if (n_per_side is None) == (point_grid is None):
+        raise ValueError('forward_prompt_points: give n_per_side or point_grid (one of them)')
+    device = forward_mask.device
+    grid = prompt_grid(n_per_side, device) if point_grid is None else point_grid
+    n = grid.shape[0]
+    if not forward_mask.is_cuda:     # (the wrapper refuses; a test's CPU statement of it answers on the host)
+        points, _, count = ops.prompt_points(forward_mask.contiguous(), grid, threshold)
+        return points[:int(count[0])].numpy().copy()
+    packed = torch.empty(2 * n + 1, dtype=torch.float32, device=device)   # the kept points, the count behind them
+    ops.prompt_points(forward_mask.contiguous(), grid, threshold, packed=packed)
+    host = _PINNED.get(n)
+    if host is None:
+        host = _PINNED[n] = torch.empty(2 * n + 1, dtype=torch.float32, pin_memory=True)
+    host.copy_(packed, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+    event.synchronize()
+    kept = int(host[2 * n:].view(torch.int32)[0])
+    return host[:2 * kept].view(kept, 2).numpy().copy()
