@@ -762,6 +762,49 @@ int deva_box_nms(const int32_t* boxes, const float* scores, int n_boxes, double 
                  void* scratch, int64_t scratch_bytes, int32_t* keep, int32_t* n_keep, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Box prompts of a text-prompted detection frame: a detector's fp32 boxes -> the boxes worth segmenting, and
+ * a segmenter's candidate masks per box -> one binary plane per box, what deva_detection_assemble (policy 2)
+ * takes.  The reference does this on the host in deva/ext/grounding_dino.py:101-115: torchvision.ops.nms on
+ * the detector's xyxy (:101-103), then per box sam.predict(box, multimask_output=True), np.argmax(scores)
+ * and a numpy mask (:110-115), i.e. three thresholded full-frame planes and a device-to-host copy per box,
+ * uploaded again plane by plane (:133).  torchvision and segment_anything are neither part of the
+ * reference's tree nor needed here: the rules below ARE the contract, and the CPU statement
+ * (tests/emu_text.py) is written from them.
+ *
+ * deva_box_nms_xyxy: rule 5 of the proposal filter (deva_proposal_finish, above) on boxes fp32 [n_boxes][4]
+ *   (x0, y0, x1, y1) AS GIVEN, without any conversion, and scores fp32 [n_boxes], both device ->
+ *   keep int32 [n_boxes] (indices in keep order) and *n_keep, both device.  The rule's parts:
+ *   N1. area = (x1-x0)*(y1-y0), no +1; an inverted box has a negative area, as torchvision computes it.
+ *   N2. inter = max(0, min(x1)-max(x0)) * max(0, min(y1)-max(y0)); ovr = inter / (area_i + area_j - inter);
+ *       every operation a rounded fp32 one, no contraction.
+ *   N3. j is suppressed by a kept i that comes before it iff (double)ovr > thresh; a NaN overlap (0 / 0, or
+ *       a NaN coordinate) suppresses nothing.
+ *   N4. The order is descending score, a NaN score before every number, among equal scores (-0.0 and 0.0
+ *       are equal) the lower index first.  The keep list is in that order.
+ *   At most 4096 boxes; scratch = deva_proposal_scratch(n_boxes) bytes of device memory, 16-byte aligned.
+ *   n_boxes == 0 sets *n_keep = 0 and touches nothing else.  The launches are deva_box_nms's own (rank,
+ *   matrix, reduce) with the box load switched: there is one NMS in the library.
+ *
+ * deva_box_mask_select: logits fp32 [batch][per_box][height][width], contiguous; scores fp32
+ *   [batch][per_box]; both device.
+ *   S1. chosen[b] is numpy's argmax of scores[b][:] (grounding_dino.py:112): the index of the first NaN if
+ *       any score is a NaN, otherwise the first maximum (-0.0 and 0.0 are equal).
+ *   S2. out plane b is x > fp32(mask_threshold) of plane chosen[b], as bytes 0 / 1 (what SamPredictor
+ *       returns for `masks`): strict, and NaN gives 0.
+ *   S3. Only the chosen plane of a box is read; the choice is made on the device, by every workgroup from
+ *       the box's scores.
+ *   out = uint8 [batch][height][width] at ANY alignment (typically a slice of a caller-owned arena); chosen
+ *   = int32 [batch], device, may be NULL.  per_box is 1..16; any batch >= 0 (more boxes than one grid
+ *   dimension holds are cut into launches; batch * per_box <= 2^30); offsets are 64-bit; a plane has at most
+ *   2^30 pixels.  One launch with grid (chunk, box) per 65535 boxes: no atomics, no LDS, no scratch memory;
+ *   the least traffic is 5 bytes per pixel and box (4 read, 1 written).
+ * Everything is checked before the first launch; all work goes on `stream`, nothing synchronises. */
+int deva_box_nms_xyxy(const float* boxes, const float* scores, int n_boxes, double thresh, void* scratch,
+                      int64_t scratch_bytes, int32_t* keep, int32_t* n_keep, void* stream);
+int deva_box_mask_select(const float* logits, const float* scores, int batch, int per_box, int height,
+                         int width, double mask_threshold, uint8_t* out, int32_t* chosen, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Prompt points of an automatic detection frame: the tracker's forward mask -> the grid points that lie on
  * background, the only ones the segmenter is asked about (the reference: deva/ext/automatic_sam.py:67-89,
  * about fifteen ATen launches, a boolean-index copy and a .cpu()).  The rules below ARE the contract; the

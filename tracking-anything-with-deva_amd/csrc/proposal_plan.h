@@ -44,4 +44,9 @@ int proposal_gather_check(const void* arena, int capacity, int height, int width
 int box_nms_check(const void* boxes, const void* scores, int m, double box_nms_thresh, const void* scratch,
                   int64_t scratch_bytes, const void* keep, const void* n_keep);
 
+// the rank / matrix / reduce launches of rule 5 on checked arguments (proposals.hip; shared with box_prompts.hip):
+// boxes int32 [n][4], or fp32 [n][4] taken as given with boxes_f32; `what` names the entry point in an error
+int box_nms_run(const char* what, const void* boxes, bool boxes_f32, const float* scores, int n_boxes, double thresh,
+                void* scratch, int32_t* keep, int32_t* n_keep, void* stream);
+
 }  // namespace deva

@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(256) prop_binarize_kernel(PropArgs a) {
 
 // ------------------------------------------------------------------------------------------ NMS
 struct NmsArgs {
-  const int32_t* boxes;   // x0, y0, x1, y1 of box i at boxes + i * box_stride
+  const int32_t* boxes;   // x0, y0, x1, y1 of box i at boxes + i * box_stride: int32 values, or the bits of fp32 ones
   const int32_t* scores;  // fp32 bits of score i at scores + i * score_stride
   int box_stride, score_stride;
   const int32_t* m_dev;  // the number of boxes lives on the device (clamped to m_max), or NULL: m_max boxes
@@ -247,6 +247,13 @@ __global__ void __launch_bounds__(256) prop_rank_kernel(NmsArgs a) {
   a.order[rank] = i;  // (a total order: every position is written once)
 }
 
+// kFloat: the boxes are fp32 as given (deva_box_nms_xyxy); otherwise int32 pixel indices, converted (rule 5)
+template <bool kFloat>
+__device__ __forceinline__ float nms_coord(int32_t v) {
+  return kFloat ? __int_as_float(v) : (float)v;
+}
+
+template <bool kFloat>
 __global__ void __launch_bounds__(256) prop_nms_matrix_kernel(NmsArgs a) {
 #pragma clang fp contract(off)
   const int m = nms_count(a);
@@ -257,8 +264,10 @@ __global__ void __launch_bounds__(256) prop_nms_matrix_kernel(NmsArgs a) {
   if (c > r && c < m) {
     const int32_t* bi = a.boxes + (int64_t)a.order[r] * a.box_stride;
     const int32_t* bj = a.boxes + (int64_t)a.order[c] * a.box_stride;
-    const float ax0 = (float)bi[0], ay0 = (float)bi[1], ax1 = (float)bi[2], ay1 = (float)bi[3];
-    const float bx0 = (float)bj[0], by0 = (float)bj[1], bx1 = (float)bj[2], by1 = (float)bj[3];
+    const float ax0 = nms_coord<kFloat>(bi[0]), ay0 = nms_coord<kFloat>(bi[1]);
+    const float ax1 = nms_coord<kFloat>(bi[2]), ay1 = nms_coord<kFloat>(bi[3]);
+    const float bx0 = nms_coord<kFloat>(bj[0]), by0 = nms_coord<kFloat>(bj[1]);
+    const float bx1 = nms_coord<kFloat>(bj[2]), by1 = nms_coord<kFloat>(bj[3]);
     const float area_i = (ax1 - ax0) * (ay1 - ay0), area_j = (bx1 - bx0) * (by1 - by0);
     const float iw = fmaxf(0.0f, fminf(ax1, bx1) - fmaxf(ax0, bx0));
     const float ih = fmaxf(0.0f, fminf(ay1, by1) - fmaxf(ay0, by0));
@@ -331,9 +340,13 @@ __global__ void __launch_bounds__(256) prop_gather_kernel(const uint8_t* arena, 
   }
 }
 
-void nms_launch(const NmsArgs& a, hipStream_t s) {
+void nms_launch(const NmsArgs& a, bool boxes_f32, hipStream_t s) {
   hipLaunchKernelGGL(prop_rank_kernel, dim3((unsigned)ceil_div(a.m_max, 256)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(prop_nms_matrix_kernel, dim3((unsigned)ceil_div(a.words, 4), (unsigned)a.m_max), dim3(256), 0, s, a);
+  const dim3 grid((unsigned)ceil_div(a.words, 4), (unsigned)a.m_max);
+  if (boxes_f32)
+    hipLaunchKernelGGL(prop_nms_matrix_kernel<true>, grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(prop_nms_matrix_kernel<false>, grid, dim3(256), 0, s, a);
   hipLaunchKernelGGL(prop_nms_reduce_kernel, dim3(1), dim3(64), 0, s, a);
 }
 
@@ -343,6 +356,28 @@ T* at(void* scratch, int64_t offset) {
 }
 
 }  // namespace
+
+// rule 5 alone on n_boxes (checked by the caller: 0..kPropMaxMasks) int32 or fp32 boxes: deva_box_nms and
+// deva_box_nms_xyxy (box_prompts.hip)
+int box_nms_run(const char* what, const void* boxes, bool boxes_f32, const float* scores, int n_boxes, double thresh,
+                void* scratch, int32_t* keep, int32_t* n_keep, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n_boxes == 0) {
+    if (hipMemsetAsync(n_keep, 0, sizeof(int32_t), s) != hipSuccess) return check_launch(what);
+    return 0;
+  }
+  const ProposalPlan p = proposal_plan(n_boxes);
+  NmsArgs a = {};
+  a.boxes = static_cast<const int32_t*>(boxes), a.scores = reinterpret_cast<const int32_t*>(scores);
+  a.box_stride = 4, a.score_stride = 1;
+  a.m_max = n_boxes, a.words = p.words;
+  a.thresh = thresh;
+  a.order = at<int32_t>(scratch, p.off_order), a.matrix = at<unsigned long long>(scratch, p.off_matrix);
+  a.keep = keep, a.n_keep = n_keep;
+  nms_launch(a, boxes_f32, s);
+  return check_launch(what);
+}
+
 }  // namespace deva
 
 using namespace deva;
@@ -399,7 +434,7 @@ extern "C" int deva_proposal_finish(int capacity, double box_nms_thresh, void* s
   a.order = at<int32_t>(scratch, p.off_order), a.matrix = at<unsigned long long>(scratch, p.off_matrix);
   a.keep = at<int32_t>(scratch, p.off_keep), a.n_keep = at<int32_t>(scratch, p.off_nkeep);
   a.result = result;
-  nms_launch(a, (hipStream_t)stream);
+  nms_launch(a, false, (hipStream_t)stream);
   return check_launch("deva_proposal_finish");
 }
 
@@ -417,18 +452,5 @@ extern "C" int deva_proposal_gather(const uint8_t* arena, int capacity, int heig
 extern "C" int deva_box_nms(const int32_t* boxes, const float* scores, int n_boxes, double box_nms_thresh, void* scratch,
                             int64_t scratch_bytes, int32_t* keep, int32_t* n_keep, void* stream) {
   if (int e = box_nms_check(boxes, scores, n_boxes, box_nms_thresh, scratch, scratch_bytes, keep, n_keep)) return e;
-  hipStream_t s = (hipStream_t)stream;
-  if (n_boxes == 0) {
-    if (hipMemsetAsync(n_keep, 0, sizeof(int32_t), s) != hipSuccess) return check_launch("deva_box_nms");
-    return 0;
-  }
-  const ProposalPlan p = proposal_plan(n_boxes);
-  NmsArgs a = {};
-  a.boxes = boxes, a.scores = reinterpret_cast<const int32_t*>(scores), a.box_stride = 4, a.score_stride = 1;
-  a.m_max = n_boxes, a.words = p.words;
-  a.thresh = box_nms_thresh;
-  a.order = at<int32_t>(scratch, p.off_order), a.matrix = at<unsigned long long>(scratch, p.off_matrix);
-  a.keep = keep, a.n_keep = n_keep;
-  nms_launch(a, s);
-  return check_launch("deva_box_nms");
+  return box_nms_run("deva_box_nms", boxes, false, scores, n_boxes, box_nms_thresh, scratch, keep, n_keep, stream);
 }

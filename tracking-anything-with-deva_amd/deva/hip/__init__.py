@@ -168,6 +168,8 @@ SIGNATURES = {
     'deva_proposal_finish': (c_int, [c_int, c_double, c_void_p, c_int64, c_void_p, c_void_p]),
     'deva_proposal_gather': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     'deva_box_nms': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'deva_box_nms_xyxy': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'deva_box_mask_select': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     'deva_prompt_scratch': (c_int64, [c_int, c_int, c_int]),
     'deva_prompt_points': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_double, c_void_p, c_int64, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),

@@ -21,6 +21,7 @@ __all__ = ['PackedConv', 'pack_conv', 'conv2d', 'conv_plan', 'ConvLaunchInfo', '
            'label_histogram', 'merge_paint', 'lut_remap', 'index_mask', 'input_head',
            'scores_u8', 'ensemble_index_mask', 'flip_w', 'frame_result', 'mask_rle', 'FrameProducts', 'detection_assemble',
            'ProposalState', 'ProposalResult', 'proposal_state', 'proposal_begin', 'proposal_batch', 'proposal_finish', 'box_nms',
+           'box_nms_xyxy', 'box_mask_select', 'BOX_MAX_PER_BOX',
            'prompt_points', 'PROMPT_MAX_POINTS',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_SQUARE_PLUS_ONE']
 
@@ -1368,6 +1369,74 @@ def box_nms(boxes: torch.Tensor, scores: torch.Tensor, box_nms_thresh: float) ->
     check(lib().deva_box_nms(bp if m else None, sp if m else None, m, float(box_nms_thresh), scratch.data_ptr() if m else None,
                              nbytes, keep.data_ptr(), keep.data_ptr() + 4 * m, _stream()), 'deva_box_nms')
     return keep[:int(keep[m])].clone()
+
+
+# ------------------------------------------------------------------------------------------ box prompts
+BOX_MAX_PER_BOX = 16
+
+
+def box_nms_xyxy(boxes: torch.Tensor, scores: torch.Tensor, thresh: float, *,
+                 packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [M,4] boxes (x0, y0, x1, y1, taken as given) and fp32 [M] scores on the device -> int32 [K] kept indices on the
+    device, in keep order: `box_nms` for a detector's float boxes (include/deva_hip.h, deva_box_nms_xyxy: torchvision's CPU
+    arithmetic; descending score, a NaN first, among equal scores the lower index).  Reading K synchronises once.
+    `packed`: the caller's int32 [M + 1] device tensor that receives the list and, behind it, the count; nothing
+    synchronises then and `packed` itself is returned (one host copy fetches both)."""
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise DevaHipError(f'box_nms_xyxy: fp32 [M,4] boxes expected (got {tuple(boxes.shape)})')
+    m = boxes.shape[0]
+    if tuple(scores.shape) != (m,):
+        raise DevaHipError(f'box_nms_xyxy: scores must be fp32 [{m}] (got {tuple(scores.shape)})')
+    if m > PROPOSAL_MAX_MASKS:
+        raise DevaHipError(f'box_nms_xyxy: at most {PROPOSAL_MAX_MASKS} boxes (got {m})')
+    thresh = float(thresh)
+    if thresh != thresh:
+        raise DevaHipError('box_nms_xyxy: the NMS threshold is not a number')
+    bp, sp = _p(boxes, name='boxes'), _p(scores, name='scores')
+    if packed is None:
+        keep = torch.empty(m + 1, dtype=torch.int32, device=boxes.device)     # the count travels behind the list
+    elif _p(packed, torch.int32, 'packed') is None or packed.numel() != m + 1:
+        raise DevaHipError(f'box_nms_xyxy: `packed` must be int32 [{m + 1}]')
+    else:
+        keep = packed
+    nbytes = lib().deva_proposal_scratch(m) if m else 0
+    scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=boxes.device)
+    check(lib().deva_box_nms_xyxy(bp if m else None, sp if m else None, m, thresh, scratch.data_ptr() if m else None,
+                                  nbytes, keep.data_ptr(), keep.data_ptr() + 4 * m, _stream()), 'deva_box_nms_xyxy')
+    if packed is not None:
+        return packed
+    return keep[:int(keep[m])].clone()
+
+
+def box_mask_select(logits: torch.Tensor, scores: torch.Tensor, mask_threshold: float = 0.0,
+                    out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 [B,M,H,W] candidate mask logits of B box prompts and their fp32 [B,M] scores on the device -> (planes uint8
+    [B,H,W] 0 / 1, chosen int32 [B]) on the device: per box the plane numpy's argmax of its scores picks (the first NaN,
+    else the first maximum), thresholded with `> mask_threshold` (include/deva_hip.h, deva_box_mask_select).  Only the
+    chosen planes are read; one launch, nothing synchronises.  `out`: the caller's contiguous uint8 [B,H,W] device
+    tensor at any alignment, e.g. a slice of an arena (default: allocated here)."""
+    if logits.dim() != 4:
+        raise DevaHipError(f'box_mask_select: [B,M,H,W] logits expected (got {tuple(logits.shape)})')
+    b, m, h, w = logits.shape
+    if not 1 <= m <= BOX_MAX_PER_BOX:
+        raise DevaHipError(f'box_mask_select: 1 to {BOX_MAX_PER_BOX} planes per box (got {m})')
+    if tuple(scores.shape) != (b, m):
+        raise DevaHipError(f'box_mask_select: scores must be fp32 [{b},{m}] (got {tuple(scores.shape)})')
+    if h <= 0 or w <= 0 or h * w > 1 << 30:
+        raise DevaHipError(f'box_mask_select: bad plane size {(h, w)}')
+    mask_threshold = float(mask_threshold)
+    if mask_threshold != mask_threshold:
+        raise DevaHipError('box_mask_select: the mask threshold is not a number')
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (b, h, w)):
+        raise DevaHipError(f'box_mask_select: `out` must be uint8 [{b},{h},{w}] (got {out.dtype} {tuple(out.shape)})')
+    lp, sp = _p(logits, name='logits'), _p(scores, name='scores')
+    if out is None:
+        out = torch.empty((b, h, w), dtype=torch.uint8, device=logits.device)
+    op = _p(out, torch.uint8, 'out')
+    chosen = torch.empty(b, dtype=torch.int32, device=logits.device)
+    check(lib().deva_box_mask_select(lp if b else None, sp if b else None, b, m, h, w, mask_threshold, op if b else None,
+                                     chosen.data_ptr() if b else None, _stream()), 'deva_box_mask_select')
+    return out, chosen
 
 
 # ------------------------------------------------------------------------------------------ prompt points

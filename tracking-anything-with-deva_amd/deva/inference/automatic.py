@@ -17,7 +17,10 @@ The segmenter is any object with
                                          frame's own size, iou_preds fp32 [B*M]), both on the device
     reset_image()                        optional
     mask_threshold                       optional attribute (default 0.0, SAM's)
-INTEGRATION.md wraps a `SamPredictor` this way."""
+INTEGRATION.md wraps a `SamPredictor` this way.
+
+`FrameLoop` is the loop itself; `deva.inference.with_text.TextPromptedProcessor` runs the same loop with detections
+from a text-prompted detector."""
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -28,7 +31,7 @@ from deva.inference.object_info import ObjectInfo
 from deva.inference.proposals import ProposalFilter
 from deva.utils.tensor_utils import frame_to_network_input
 
-__all__ = ['AutomaticProcessor', 'BufferedFrame', 'CONFIG_KEYS']
+__all__ = ['AutomaticProcessor', 'BufferedFrame', 'FrameLoop', 'CONFIG_KEYS']
 
 CONFIG_KEYS = ('size', 'suppress_small_objects', 'temporal_setting', 'num_voting_frames', 'detection_every',
                'SAM_NUM_POINTS_PER_SIDE', 'SAM_NUM_POINTS_PER_BATCH', 'SAM_PRED_IOU_THRESHOLD', 'SAM_OVERLAP_THRESHOLD')
@@ -46,22 +49,91 @@ class BufferedFrame:
     shape = property(lambda self: self.info['shape'])
 
 
-class AutomaticProcessor:
-    """`process_frame_automatic` and `flush_buffer` of the reference's demo as one object around a `DEVAInferenceCore`.
+class FrameLoop:
+    """The frame loop that the reference's two demos share, and `flush_buffer`, around a `DEVAInferenceCore`:
+    automatic_processor.py:28-128 and with_text_processor.py:30-122 differ only in how a detection is made and in the
+    keywords of `incorporate_detection`.  A processor gives `config_keys`, `incorporate_keywords` and
+    `_detect(image, image_np) -> (index mask, [ObjectInfo])`.
 
-    The configuration is `core.config`; every key of `CONFIG_KEYS` must be there (a missing one raises KeyError with its
-    name: no default is invented).  `capacity` is the `ProposalFilter`'s (masks that may pass the drops in one frame).
+    The configuration is `core.config`; every key of `config_keys` must be there (a missing one raises KeyError with its
+    name: no default is invented).
     `saver`: anything with `save_mask(prob, frame_name, need_resize=, shape=, image_np=)`, e.g. `FrameResultSaver`.
-    `next_voting_frame` starts at num_voting_frames - 1, as the demo sets it."""
+    `next_voting_frame` starts at num_voting_frames - 1, as the demos set it."""
+    config_keys: Tuple[str, ...] = ()
+    incorporate_keywords: Dict = {}
 
-    def __init__(self, core, segmenter, *, capacity: int = 512, saver=None):
-        self.core, self.segmenter, self.capacity, self.saver = core, segmenter, int(capacity), saver
-        for key in CONFIG_KEYS:
+    def __init__(self, core, saver=None):
+        self.core, self.saver = core, saver
+        for key in self.config_keys:
             if key not in core.config:
                 raise KeyError(key)
         if core.config['temporal_setting'] not in ('online', 'semionline'):
             raise ValueError(f"temporal_setting must be 'online' or 'semionline' (got {core.config['temporal_setting']!r})")
         self.next_voting_frame = core.config['num_voting_frames'] - 1
+
+    def _detect(self, image: torch.Tensor, image_np: np.ndarray) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+        raise NotImplementedError
+
+    def _emit(self, produced: List, prob: torch.Tensor, frame_name: str, image_np: np.ndarray) -> None:
+        produced.append((frame_name, prob))
+        if self.saver is not None:
+            h, w = image_np.shape[:2]
+            self.saver.save_mask(prob, frame_name, need_resize=self.core.config['size'] > 0, shape=(h, w), image_np=image_np)
+
+    def process_frame(self, image_np: np.ndarray, ti: int, frame_name: str) -> List[Tuple[str, torch.Tensor]]:
+        """one frame of the video (RGB uint8 H*W*3) -> the (frame name, probabilities) pairs this call produced: one in
+        the online setting; none, one or a voting window's worth in the semi-online one"""
+        core, cfg = self.core, self.core.config
+        h, w = image_np.shape[:2]
+        image = frame_to_network_input(image_np, cfg['size'], antialias=False)   # the demo's rule (demo_utils.py:10-19)
+        produced: List[Tuple[str, torch.Tensor]] = []
+        if cfg['temporal_setting'] == 'semionline':
+            if ti + cfg['num_voting_frames'] > self.next_voting_frame:
+                mask, segments_info = self._detect(image, image_np)
+                info = {'frame': [frame_name], 'shape': [h, w]}
+                core.add_to_temporary_buffer(BufferedFrame(image, mask, segments_info, ti, info, image_np))   # wait for more
+                if ti == self.next_voting_frame:
+                    first = core.frame_buffer[0]
+                    _, mask, new_segments_info = core.vote_in_temporary_buffer(keyframe_selection='first')
+                    prob = core.incorporate_detection(first.image, mask, new_segments_info, **self.incorporate_keywords)
+                    self.next_voting_frame += cfg['detection_every']
+                    self._emit(produced, prob, first.name, first.image_np)
+                    for frame in core.frame_buffer[1:]:
+                        self._emit(produced, core.step(frame.image, None, None), frame.name, frame.image_np)
+                    core.clear_buffer()
+            else:
+                self._emit(produced, core.step(image, None, None), frame_name, image_np)    # standard propagation
+        elif cfg['temporal_setting'] == 'online':
+            if ti % cfg['detection_every'] == 0:
+                mask, segments_info = self._detect(image, image_np)
+                prob = core.incorporate_detection(image, mask, segments_info, **self.incorporate_keywords)
+            else:
+                prob = core.step(image, None, None)
+            self._emit(produced, prob, frame_name, image_np)
+        else:
+            raise ValueError(f"temporal_setting must be 'online' or 'semionline' (got {cfg['temporal_setting']!r})")
+        return produced
+
+    def flush(self) -> List[Tuple[str, torch.Tensor]]:
+        """`flush_buffer` (demo_utils.py:22-46): step the frames that are still buffered when the video ends"""
+        produced: List[Tuple[str, torch.Tensor]] = []
+        for frame in self.core.frame_buffer:
+            self._emit(produced, self.core.step(frame.image, None, None), frame.name, frame.image_np)
+        return produced
+
+
+class AutomaticProcessor(FrameLoop):
+    """`process_frame_automatic` and `flush_buffer` of the reference's demo as one object around a `DEVAInferenceCore`
+    (the loop is `FrameLoop`'s; a detection is incorporated with `incremental=True`).
+
+    Every key of `CONFIG_KEYS` must be in `core.config`.  `capacity` is the `ProposalFilter`'s (masks that may pass the
+    drops in one frame)."""
+    config_keys = CONFIG_KEYS
+    incorporate_keywords = {'incremental': True}
+
+    def __init__(self, core, segmenter, *, capacity: int = 512, saver=None):
+        super().__init__(core, saver)
+        self.segmenter, self.capacity = segmenter, int(capacity)
         self._filter = None
 
     # ------------------------------------------------------------------ auto_segment
@@ -106,54 +178,7 @@ class AutomaticProcessor:
                                              suppress_small_objects=cfg['suppress_small_objects'],
                                              overlap_threshold=cfg['SAM_OVERLAP_THRESHOLD'])
 
-    # ------------------------------------------------------------------ process_frame_automatic
-    def _emit(self, produced: List, prob: torch.Tensor, frame_name: str, image_np: np.ndarray) -> None:
-        produced.append((frame_name, prob))
-        if self.saver is not None:
-            h, w = image_np.shape[:2]
-            self.saver.save_mask(prob, frame_name, need_resize=self.core.config['size'] > 0, shape=(h, w), image_np=image_np)
-
+    # ------------------------------------------------------------------ make_segmentation (automatic_processor.py)
     def _detect(self, image: torch.Tensor, image_np: np.ndarray) -> Tuple[torch.Tensor, List[ObjectInfo]]:
         forward_mask = detections.estimate_forward_mask(self.core, image) if self.core.memory.engaged else None
         return self.segment(image_np, forward_mask, device=image.device)
-
-    def process_frame(self, image_np: np.ndarray, ti: int, frame_name: str) -> List[Tuple[str, torch.Tensor]]:
-        """one frame of the video (RGB uint8 H*W*3) -> the (frame name, probabilities) pairs this call produced: one in
-        the online setting; none, one or a voting window's worth in the semi-online one"""
-        core, cfg = self.core, self.core.config
-        h, w = image_np.shape[:2]
-        image = frame_to_network_input(image_np, cfg['size'], antialias=False)   # the demo's rule (demo_utils.py:10-19)
-        produced: List[Tuple[str, torch.Tensor]] = []
-        if cfg['temporal_setting'] == 'semionline':
-            if ti + cfg['num_voting_frames'] > self.next_voting_frame:
-                mask, segments_info = self._detect(image, image_np)
-                info = {'frame': [frame_name], 'shape': [h, w]}
-                core.add_to_temporary_buffer(BufferedFrame(image, mask, segments_info, ti, info, image_np))   # wait for more
-                if ti == self.next_voting_frame:
-                    first = core.frame_buffer[0]
-                    _, mask, new_segments_info = core.vote_in_temporary_buffer(keyframe_selection='first')
-                    prob = core.incorporate_detection(first.image, mask, new_segments_info, incremental=True)
-                    self.next_voting_frame += cfg['detection_every']
-                    self._emit(produced, prob, first.name, first.image_np)
-                    for frame in core.frame_buffer[1:]:
-                        self._emit(produced, core.step(frame.image, None, None), frame.name, frame.image_np)
-                    core.clear_buffer()
-            else:
-                self._emit(produced, core.step(image, None, None), frame_name, image_np)    # standard propagation
-        elif cfg['temporal_setting'] == 'online':
-            if ti % cfg['detection_every'] == 0:
-                mask, segments_info = self._detect(image, image_np)
-                prob = core.incorporate_detection(image, mask, segments_info, incremental=True)
-            else:
-                prob = core.step(image, None, None)
-            self._emit(produced, prob, frame_name, image_np)
-        else:
-            raise ValueError(f"temporal_setting must be 'online' or 'semionline' (got {cfg['temporal_setting']!r})")
-        return produced
-
-    def flush(self) -> List[Tuple[str, torch.Tensor]]:
-        """`flush_buffer` (demo_utils.py:22-46): step the frames that are still buffered when the video ends"""
-        produced: List[Tuple[str, torch.Tensor]] = []
-        for frame in self.core.frame_buffer:
-            self._emit(produced, self.core.step(frame.image, None, None), frame.name, frame.image_np)
-        return produced

@@ -22,7 +22,12 @@ Choosing prompt points from a forward mask (automatic_sam.py:67-89) feeds the de
 it on the device (`ops.prompt_points`: three launches and one copy of 8 bytes per point) from the mask that
 `estimate_forward_mask` gives.  The masks and scores of `assemble_automatic` come out of
 `deva.inference.proposals.ProposalFilter`, which filters a promptable segmenter's raw logits on the device;
-`deva.inference.automatic.AutomaticProcessor` ties all of it into the reference's frame loop."""
+`deva.inference.automatic.AutomaticProcessor` ties all of it into the reference's frame loop.
+
+The text-prompted path (grounding_dino.py:101-142) is `text_detections`: the detector's fp32 boxes through
+`ops.box_nms_xyxy`, the kept ones to a box-prompted segmenter batch by batch, the best candidate mask per box chosen and
+binarised on the device by `ops.box_mask_select`, then `assemble_with_text`: two small host copies per detection frame.
+`deva.inference.with_text.TextPromptedProcessor` is its frame loop."""
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -167,3 +172,74 @@ def forward_prompt_points(forward_mask: torch.Tensor, n_per_side: Optional[int] 
     event.synchronize()
     kept = int(host[2 * n:].view(torch.int32)[0])
     return host[:2 * kept].view(kept, 2).numpy().copy()
+
+
+# ------------------------------------------------------------------------------------------ text-prompted detections
+def _host_array(values, dtype) -> np.ndarray:
+    if torch.is_tensor(values):
+        values = values.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(values, dtype=dtype))
+
+
+def text_detections(boxes, confidences, class_ids, segmenter, frame_hw: Tuple[int, int], size: Tuple[int, int], *,
+                    nms_threshold: float, boxes_per_batch: int = 16, capacity: int = 256,
+                    arena: Optional[torch.Tensor] = None, device=None) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+    """`segment_with_text` from the detector's answer on (grounding_dino.py:101-142): `boxes` fp32 [N,4] xyxy in pixels
+    of the frame, `confidences` fp32 [N], `class_ids` [N] (numpy, as GroundingDINO's wrapper returns them, or tensors; a
+    class id may be None, the unmatched phrase, and passes through) -> (int64 [OH,OW] index mask on the device,
+    [ObjectInfo(id, category_id, score)] in paint order).
+
+    Box NMS runs on the device (`ops.box_nms_xyxy`); ONE small copy brings the keep list and its count to the host, which
+    needs the count to batch the segmenter and reorders `confidences` / `class_ids` from it.  The kept boxes are
+    gathered on the device and go to `segmenter.predict_boxes` in batches of `boxes_per_batch`; every batch goes
+    straight into `ops.box_mask_select`, which writes the chosen byte planes into the arena (`arena`: the caller's
+    contiguous uint8 [capacity,H,W]; default: allocated here for the kept boxes).  Nothing synchronises per batch.
+    `assemble_with_text` then makes its one copy of the record table.  The segmenter must have seen the frame
+    (`set_image`); it is not asked at all when no box is given or kept.  More kept boxes than `capacity` raise
+    DevaHipError before the segmenter is asked."""
+    h, w = int(frame_hw[0]), int(frame_hw[1])
+    size = (int(size[0]), int(size[1]))
+    if device is None:
+        device = arena.device if arena is not None else (boxes.device if torch.is_tensor(boxes) else torch.device('cuda'))
+    if torch.is_tensor(boxes):
+        boxes_dev = boxes.detach().to(device=device, dtype=torch.float32).reshape(-1, 4).contiguous()
+    else:
+        boxes_dev = torch.from_numpy(_host_array(boxes, np.float32).reshape(-1, 4)).to(device)
+    n = boxes_dev.shape[0]
+    conf_host = _host_array(confidences, np.float32).reshape(-1)
+    classes = class_ids.tolist() if hasattr(class_ids, 'tolist') else list(class_ids)
+    if conf_host.shape[0] != n or len(classes) != n:
+        raise ValueError(f'text_detections: {n} boxes, {conf_host.shape[0]} confidences and {len(classes)} class ids')
+    per_batch = int(boxes_per_batch)
+    if per_batch < 1:
+        raise ValueError(f'text_detections: at least one box per batch (got {boxes_per_batch})')
+    if arena is not None and (arena.dtype != torch.uint8 or arena.numel() != capacity * h * w or not arena.is_contiguous()):
+        raise ops.DevaHipError(f'text_detections: the arena must be a contiguous uint8 tensor of {capacity} x {h} x {w}')
+    if n == 0:
+        return torch.zeros(size, dtype=torch.int64, device=device), []
+    conf_dev = torch.from_numpy(conf_host).to(device)
+    packed = ops.box_nms_xyxy(boxes_dev, conf_dev, nms_threshold,
+                              packed=torch.empty(n + 1, dtype=torch.int32, device=device))
+    if packed.is_cuda:
+        host = torch.empty(n + 1, dtype=torch.int32, pin_memory=True)
+        host.copy_(packed, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record()
+        event.synchronize()
+    else:
+        host = packed
+    kept = int(host[n])
+    keep = host[:kept].tolist()
+    if kept > capacity:
+        raise ops.DevaHipError(f'text_detections: {kept} boxes are left after NMS, the arena holds {capacity} '
+                               '(raise `capacity`, or the detector\'s thresholds)')
+    if kept == 0:
+        return torch.zeros(size, dtype=torch.int64, device=device), []
+    planes = (torch.empty((kept, h, w), dtype=torch.uint8, device=device) if arena is None
+              else arena.view(capacity, h, w)[:kept])
+    boxes_px = boxes_dev.index_select(0, packed[:kept].to(torch.int64))
+    threshold = getattr(segmenter, 'mask_threshold', 0.0)
+    for first in range(0, kept, per_batch):
+        logits, scores = segmenter.predict_boxes(boxes_px[first:first + per_batch])
+        ops.box_mask_select(logits, scores, threshold, out=planes[first:first + logits.shape[0]])
+    return assemble_with_text(planes, [conf_host[k] for k in keep], [classes[k] for k in keep], size)
