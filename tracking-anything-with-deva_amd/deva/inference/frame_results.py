@@ -104,6 +104,7 @@ class FrameResult:
     blend: Optional[torch.Tensor] = None     # uint8 [H,W,3] overlay on the frame
     index: Optional[torch.Tensor] = None     # int16 [H,W] channel (tmp id) plane
     host: Dict[str, np.ndarray] = field(default_factory=dict)   # planes the caller asked to be copied to the host
+    channel_ids: Optional[np.ndarray] = None  # int64 [C] the id that each channel of `index` was given in this frame
 
 
 def _to_host(t: torch.Tensor) -> torch.Tensor:
@@ -121,6 +122,7 @@ class PendingFrame:
     def __init__(self, size, products, segments, tmp_ids, host_stats, n, host_bounds, host_planes, event):
         self.size, self.products, self.segments, self.tmp_ids = size, products, segments, tmp_ids
         self.host_stats, self.n, self.host_bounds, self.host_planes, self.event = host_stats, n, host_bounds, host_planes, event
+        self.channel_ids = None
 
     def finish(self) -> FrameResult:
         if self.event is not None:
@@ -137,17 +139,19 @@ class PendingFrame:
             records.append(rec)
         p = self.products
         return FrameResult(size=self.size, segments=records, labels=p.labels, gray=p.gray, color=p.color, blend=p.blend,
-                           index=p.index, host={k: v.numpy() for k, v in self.host_planes.items()})
+                           index=p.index, host={k: v.numpy() for k, v in self.host_planes.items()},
+                           channel_ids=self.channel_ids)
 
 
 def launch_frame(object_manager, prob: torch.Tensor, size=None, *, image=None, rle: bool = False, color=None,
                  labels: bool = False, remap: bool = True, planes: Optional[Sequence[str]] = None,
-                 host: Sequence[str] = ()) -> PendingFrame:
+                 host: Sequence[str] = (), id_map: Optional[Dict[int, int]] = None, index: bool = False) -> PendingFrame:
     """start one frame's result on the current stream.  `color`: None = the object manager's mode (long ids: the RGB
     id image; short ids: the gray id plane), 'id' = the long-id image, 'gray', or a uint8 [K,3] palette indexed by
     id % K.  `image` (uint8 [H,W,3], numpy or tensor) adds the overlay.  `planes` overrides which of gray / color / blend
     are produced, `host` names the planes whose copy to pinned host memory is started as well.  The object table is
-    read now: later changes to it do not reach this frame."""
+    read now: later changes to it do not reach this frame.  `id_map` (object id -> id to write) replaces the ids of the
+    table and of the colours for this frame (the stuff merging of a VIPSeg run); `index` keeps the channel plane."""
     prob = prob.contiguous()
     c = prob.shape[0]
     oh, ow = tuple(prob.shape[-2:]) if size is None else (int(size[0]), int(size[1]))
@@ -158,7 +162,9 @@ def launch_frame(object_manager, prob: torch.Tensor, size=None, *, image=None, r
         ids = np.zeros(c, dtype=np.int64)
         for tmp, obj in object_manager.tmp_id_to_obj.items():
             if tmp < c:
-                ids[tmp] = int(obj.id)
+                ids[tmp] = int(obj.id) if id_map is None else int(id_map.get(int(obj.id), obj.id))
+        if id_map is not None:
+            table = torch.from_numpy(ids).to(device)
     if color is None:
         color = 'id' if object_manager.use_long_id else 'gray'
     if isinstance(color, str):
@@ -171,7 +177,7 @@ def launch_frame(object_manager, prob: torch.Tensor, size=None, *, image=None, r
         color = 'id'
     if planes is None:
         planes = (['gray'] if color == 'gray' else ['color']) + (['blend'] if image is not None else [])
-    want = list(planes) + ['stats'] + (['index'] if rle else []) + (['labels'] if labels else [])
+    want = list(planes) + ['stats'] + (['index'] if rle or index else []) + (['labels'] if labels else [])
     color_lut = torch.from_numpy(colors).to(device) if ('color' in want or 'blend' in want) else None
     if 'blend' in want:
         if image is None:
@@ -191,7 +197,9 @@ def launch_frame(object_manager, prob: torch.Tensor, size=None, *, image=None, r
         event.record()
     segments = object_manager.get_current_segments_info()      # fresh dicts of plain values: a snapshot
     tmp_ids = [tmp for _, tmp in object_manager.obj_to_tmp_id.items()]
-    return PendingFrame((oh, ow), products, segments, tmp_ids, host_stats, n, host_bounds, host_planes, event)
+    pending = PendingFrame((oh, ow), products, segments, tmp_ids, host_stats, n, host_bounds, host_planes, event)
+    pending.channel_ids = ids
+    return pending
 
 
 # ------------------------------------------------------------------------------------------ saver
@@ -199,14 +207,26 @@ class FrameResultSaver:
     """`ResultSaver` (result_utils.py:22-123) on the fused tail: the same constructor, `save_mask` (without `prompts`)
     and `end`, the same files and the same `video_json` / `all_annotations`.  `save_mask` launches the frame's kernels
     on the caller's stream, starts the copies of what the dataset needs into pinned memory and hands them to a worker
-    thread, which waits for the copies, builds the annotation and writes the files with PIL."""
+    thread, which waits for the copies, builds the annotation and writes the files with PIL.
 
-    def __init__(self, output_root: str, video_name: str, *, dataset: str, object_manager, palette=None):
+    `id_postprocessor` (dataset 'vipseg' only; None: nothing changes) is a `panoptic_quality.StuffMerger`: the id table
+    and the colour table of every frame then carry the merged ids and the merged areas are sums of the channel areas, so
+    the PNG and the `video_json` are what the reference's merge_stuff would have written from the unmerged output,
+    without reading a plane twice or re-writing a file.  `frame_hook(frame_name, result, annotation)` is called by the
+    worker after a frame's files are written, with the `FrameResult` (its `index` plane and `channel_ids` included) and
+    the annotation just appended: where an online scorer is fed."""
+
+    def __init__(self, output_root: str, video_name: str, *, dataset: str, object_manager, palette=None,
+                 id_postprocessor=None, frame_hook=None):
         self.output_root = output_root
         self.video_name = video_name
         self.dataset = dataset.lower()
         self.palette = palette
         self.object_manager = object_manager
+        self.id_postprocessor = id_postprocessor
+        self.frame_hook = frame_hook
+        if id_postprocessor is not None and self.dataset != 'vipseg':
+            raise ValueError("id_postprocessor: the stuff merging belongs to dataset 'vipseg'")
         self.need_remapping = False
         self.json_style = None
         self.output_postfix = None
@@ -258,10 +278,14 @@ class FrameResultSaver:
                     from PIL import Image
                     image_np = np.array(Image.open(path_to_image))
                 planes.append('blend')
+        merge = None
+        if self.id_postprocessor is not None:   # ids are allotted now: they go into this frame's tables
+            merge = self.id_postprocessor.assign(self.object_manager.get_current_segments_info())
         pending = launch_frame(self.object_manager, prob, shape if need_resize else None,
                                image=image_np if 'blend' in planes else None, rle=self.json_style == 'burst',
-                               color='id' if long_id else 'gray', remap=self.need_remapping, planes=planes, host=planes)
-        self.queue.put((pending, frame_name, long_id))
+                               color='id' if long_id else 'gray', remap=self.need_remapping, planes=planes, host=planes,
+                               id_map=None if merge is None else merge[0], index=self.frame_hook is not None)
+        self.queue.put((pending, frame_name, long_id) if merge is None else (pending, frame_name, long_id, merge))
 
     def end(self) -> None:
         self.queue.put(None)
@@ -291,11 +315,16 @@ class FrameResultSaver:
         os.makedirs(out, exist_ok=True)
         return out
 
-    def _write(self, pending: PendingFrame, frame_name: str, long_id: bool) -> None:
+    def _write(self, pending: PendingFrame, frame_name: str, long_id: bool, merge=None) -> None:
         from PIL import Image
         result = pending.finish()
         live = [s for s in result.segments if s['area'] > 0]     # zero-area segments are filtered out
-        if self.json_style == 'vipseg':
+        if merge is not None:   # merge_stuff's annotation: the areas of a merged id are sums of its channels' areas
+            id_map, stuff = merge
+            self.all_annotations.append({
+                'file_name': frame_name[:-4] + '.jpg',
+                'segments_info': self.id_postprocessor.annotation(live, id_map, stuff, {s['id']: s['area'] for s in live})})
+        elif self.json_style == 'vipseg':
             self.all_annotations.append({
                 'file_name': frame_name[:-4] + '.jpg',
                 'segments_info': [{'category_id': s['category_id'], 'id': s['id'], 'score': s['score'], 'area': s['area']}
@@ -311,11 +340,14 @@ class FrameResultSaver:
             if self.palette is not None:
                 out_img.putpalette(self.palette)
         else:
-            return
-        self._save_image(out_img, path.join(self._out_dir(self.output_postfix), frame_name[:-4] + '.png'))
-        if 'blend' in result.host:
-            self._save_image(Image.fromarray(result.host['blend']),
-                             path.join(self._out_dir(self.visualize_postfix), frame_name[:-4] + '.jpg'))
+            out_img = None
+        if out_img is not None:
+            self._save_image(out_img, path.join(self._out_dir(self.output_postfix), frame_name[:-4] + '.png'))
+            if 'blend' in result.host:
+                self._save_image(Image.fromarray(result.host['blend']),
+                                 path.join(self._out_dir(self.visualize_postfix), frame_name[:-4] + '.jpg'))
+        if self.frame_hook is not None:
+            self.frame_hook(frame_name, result, self.all_annotations[-1] if self.json_style is not None else None)
 
     def _save_image(self, image, where: str) -> None:
         image.save(where)
