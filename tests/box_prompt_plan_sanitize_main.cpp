@@ -1,4 +1,4 @@
-// Stand-alone host program for tests/test_box_prompt_plan_sanitize_cpu.py: the HIP-free side of the box prompts
+// Stand-alone host program for tests/test_plan_sanitize_cpu.py: the HIP-free side of the box prompts
 // (csrc/box_prompt_plan.cpp: the argument checks of deva_box_nms_xyxy and deva_box_mask_select and the launch geometry of
 // the latter) walked over the product of its boundary values under the host sanitizers.  Addresses are made up: nothing
 // is dereferenced.

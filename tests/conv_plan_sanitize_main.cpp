@@ -1,5 +1,5 @@
 // Stand-alone driver of the HIP-free convolution code (csrc/conv_plan.cpp, csrc/conv_pack.cpp) for a host build with
-// -fsanitize=address,undefined (tests/test_conv_plan_sanitize_cpu.py compiles and runs it): the planner over the product
+// -fsanitize=address,undefined (tests/test_plan_sanitize_cpu.py compiles and runs it): the planner over the product
 // of its boundary values with made-up addresses, the packers into buffers of exactly the size they ask for.  Exit 0 = no
 // sanitizer report and every invariant below held.
 #include <stdarg.h>

@@ -1,4 +1,4 @@
-// Stand-alone host program for tests/test_detection_plan_sanitize_cpu.py: the HIP-free side of deva_detection_assemble
+// Stand-alone host program for tests/test_plan_sanitize_cpu.py: the HIP-free side of deva_detection_assemble
 // (csrc/detection_plan.cpp: the argument checks and the scratch layout, and deva_detection_scratch) walked over the
 // product of its boundary values under the host sanitizers.  Addresses are made up: nothing is dereferenced.
 #include <stdarg.h>

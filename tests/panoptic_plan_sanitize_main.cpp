@@ -1,4 +1,4 @@
-// Stand-alone host program for tests/test_panoptic_plan_sanitize_cpu.py: the HIP-free side of the joint count
+// Stand-alone host program for tests/test_plan_sanitize_cpu.py: the HIP-free side of the joint count
 // (csrc/metrics/panoptic_plan.cpp: every argument check of deva_metrics_panoptic_counts and the launch decision behind
 // deva_metrics_panoptic_plan) walked over the product of its boundary values under the host sanitizers.  Addresses are
 // made up: nothing is dereferenced.

@@ -1,4 +1,4 @@
-// Stand-alone host program for tests/test_prompt_plan_sanitize_cpu.py: the HIP-free side of the prompt-point choice
+// Stand-alone host program for tests/test_plan_sanitize_cpu.py: the HIP-free side of the prompt-point choice
 // (csrc/prompt_plan.cpp: the argument checks of deva_prompt_points, the scratch layout and deva_prompt_scratch) walked
 // over the product of its boundary values under the host sanitizers.  Addresses are made up: nothing is dereferenced.
 #include <stdarg.h>

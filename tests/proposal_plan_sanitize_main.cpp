@@ -1,4 +1,4 @@
-// Stand-alone host program for tests/test_proposal_plan_sanitize_cpu.py: the HIP-free side of the proposal filter
+// Stand-alone host program for tests/test_plan_sanitize_cpu.py: the HIP-free side of the proposal filter
 // (csrc/proposal_plan.cpp: the argument checks of its five launching entry points, the scratch layout and
 // deva_proposal_scratch) walked over the product of its boundary values under the host sanitizers.  Addresses are
 // made up: nothing is dereferenced.

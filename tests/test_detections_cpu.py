@@ -2,14 +2,13 @@
 `deva.inference.detections` on the emulated op (tests/emu_detections.py) against what the reference's own auto_segment
 and segment_with_text returned for the same masks (tests/golden/detection_assembly.npz, made by
 tests/golden/make_detection_golden.py on the case of tests/detection_case.py)."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_util
 import detection_case as DC
 import emu_detections as ED
 import emu_ops
@@ -33,19 +32,8 @@ def golden(golden_dir):
 
 # ------------------------------------------------------------------------------------------ ABI
 def test_entry_points_are_exported_declared_and_bound():
-    from deva import hip
     from deva.hip import ops
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    handle = ctypes.CDLL(hip.LIB_PATH)
-    header = open(os.path.join(ROOT, 'include', 'deva_hip.h')).read()
-    for name in NAMES:
-        assert hasattr(handle, name), f'{name} not exported'
-        assert re.search(r'\bint(?:64_t)? ' + name + r'\s*\(', header), f'{name} not declared'
-        assert name in hip.SIGNATURES
-    assert hip.ABI_VERSION == 11 and hip.lib().deva_hip_version() == 11  # additive: the version does not move
-    assert re.search(r'#define DEVA_HIP_ABI_VERSION 11\b', header)
+    header = abi_util.inference_entry_points(NAMES)
     assert 'detection_assemble' in ops.__all__
     for ref in ('automatic_sam.py:106-127', 'automatic_sam.py:128-143', 'grounding_dino.py:124-140'):
         assert ref in header, ref

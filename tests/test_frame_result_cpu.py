@@ -12,6 +12,7 @@ import pytest
 import torch
 from PIL import Image
 
+import abi_util
 import emu_frame_result as E
 import emu_ops
 import full_frame_shapes as FS
@@ -30,19 +31,8 @@ def emu(monkeypatch):
 
 # ------------------------------------------------------------------------------------------ ABI
 def test_entry_points_are_exported_declared_and_bound():
-    from deva import hip
     from deva.hip import ops
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    handle = ctypes.CDLL(hip.LIB_PATH)
-    header = open(os.path.join(ROOT, 'include', 'deva_hip.h')).read()
-    for name in NAMES:
-        assert hasattr(handle, name), f'{name} not exported'
-        assert re.search(r'\bint(?:64_t)? ' + name + r'\s*\(', header), f'{name} not declared'
-        assert name in hip.SIGNATURES
-    assert hip.ABI_VERSION == 11 and hip.lib().deva_hip_version() == 11  # additive: the version does not move
-    assert re.search(r'#define DEVA_HIP_ABI_VERSION 11\b', header)
+    abi_util.inference_entry_points(NAMES)
     assert 'frame_result' in ops.__all__ and 'mask_rle' in ops.__all__
 
 

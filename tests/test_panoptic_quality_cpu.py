@@ -14,6 +14,7 @@ import pytest
 import torch
 from PIL import Image
 
+import abi_util
 import emu_frame_result as EF
 import emu_ops
 import emu_panoptic as EP
@@ -34,30 +35,15 @@ def emu(monkeypatch):
 
 def _built():
     from deva.hip import metrics
-    if not os.path.exists(metrics.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return metrics
-
-
-def _declared(header):
-    text = open(header).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    text = re.sub(r'//[^\n]*', '', text)
-    return sorted(set(re.findall(r'\b(deva_[a-z0-9_]+)\s*\(', text)))
-
-
-def _exported(lib_path):
-    out = subprocess.run(['nm', '-D', '--defined-only', lib_path], capture_output=True, text=True, check=True).stdout
-    return sorted(set(re.findall(r'\bT (deva_[a-z0-9_]+)$', out, flags=re.M))), out
+    return abi_util.built(metrics)
 
 
 # ------------------------------------------------------------------------------------------ ABI
 def test_exports_header_and_binding_are_one_list():
     metrics = _built()
-    exported, _ = _exported(metrics.LIB_PATH)
+    exported, _ = abi_util.exported(metrics.LIB_PATH)
     want = ['deva_metrics_last_error', 'deva_metrics_panoptic_counts', 'deva_metrics_panoptic_plan', 'deva_metrics_version']
-    assert exported == _declared(HEADER) == sorted(metrics.SIGNATURES) == want
+    assert exported == abi_util.declared(HEADER) == sorted(metrics.SIGNATURES) == want
     header = open(HEADER).read()
     assert re.search(r'#define DEVA_METRICS_ABI_VERSION 1\b', header)
     assert metrics.ABI_VERSION == 1 and metrics.lib().deva_metrics_version() == 1
@@ -85,12 +71,11 @@ def test_plan_mirror_has_the_c_layout(tmp_path):
 def test_the_inference_library_is_untouched_and_shares_no_symbol():
     from deva import hip
     metrics = _built()
-    hip_exported, hip_all = _exported(hip.LIB_PATH)
+    hip_exported, hip_all = abi_util.exported(hip.LIB_PATH)
     assert len(hip_exported) == 80 and hip_exported == sorted(hip.SIGNATURES)
     assert not any(n.startswith('deva_metrics') for n in hip_exported)
-    _, metrics_all = _exported(metrics.LIB_PATH)
-    defined = lambda text: set(re.findall(r'\b[TDBW] (\S+)$', text, flags=re.M))   # noqa: E731
-    shared = {s for s in defined(hip_all) & defined(metrics_all) if 'deva' in s}
+    _, metrics_all = abi_util.exported(metrics.LIB_PATH)
+    shared = {s for s in hip_all & metrics_all if 'deva' in s}
     assert not shared, shared
 
 

@@ -2,7 +2,6 @@
 errors, the CPU contract (tests/emu_prompts.py) against torch's own F.interpolate + F.grid_sample and against what the
 REFERENCE's auto_segment kept (tests/golden/prompt_points.npz), and `AutomaticProcessor` on the emulated ops against a
 straight-line restatement of the reference's loop (deva/ext/automatic_processor.py:28-128, demo_utils.py:22-46)."""
-import ctypes
 import os
 import re
 
@@ -11,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import abi_util
 import emu_detections as ED
 import emu_ops
 import emu_prompts as EM
@@ -34,19 +34,8 @@ def emu(monkeypatch):
 
 # ------------------------------------------------------------------------------------------ ABI
 def test_entry_points_are_exported_declared_and_bound():
-    from deva import hip
     from deva.hip import ops
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    handle = ctypes.CDLL(hip.LIB_PATH)
-    header = open(os.path.join(ROOT, 'include', 'deva_hip.h')).read()
-    for name in NAMES:
-        assert hasattr(handle, name), f'{name} not exported'
-        assert re.search(r'\bint(?:64_t)? ' + name + r'\s*\(', header), f'{name} not declared'
-        assert name in hip.SIGNATURES
-    assert hip.ABI_VERSION == 11 and hip.lib().deva_hip_version() == 11  # additive: the version does not move
-    assert re.search(r'#define DEVA_HIP_ABI_VERSION 11\b', header)
+    header = abi_util.inference_entry_points(NAMES)
     assert 'prompt_points' in ops.__all__
     for ref in ('automatic_sam.py:67-89', 'automatic_sam.py:69', 'automatic_sam.py:70-73', 'automatic_sam.py:80',
                 'automatic_sam.py:82'):

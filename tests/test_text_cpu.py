@@ -3,7 +3,6 @@ errors, the CPU contract (tests/emu_text.py) by hand and against the integer NMS
 REFERENCE's segment_with_text produced (tests/golden/text_segmentation.npz), and `TextPromptedProcessor` on the emulated
 ops against a straight-line restatement of the reference's loop (deva/ext/with_text_processor.py:30-122,
 demo_utils.py:22-46)."""
-import ctypes
 import os
 import re
 
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_util
 import emu_detections as ED
 import emu_ops
 import emu_proposals as EP
@@ -36,17 +36,7 @@ def emu(monkeypatch):
 def test_entry_points_are_exported_declared_and_bound():
     from deva import hip
     from deva.hip import ops
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    handle = ctypes.CDLL(hip.LIB_PATH)
-    header = open(os.path.join(ROOT, 'include', 'deva_hip.h')).read()
-    for name in NAMES:
-        assert hasattr(handle, name), f'{name} not exported'
-        assert re.search(r'\bint ' + name + r'\s*\(', header), f'{name} not declared'
-        assert name in hip.SIGNATURES
-    assert hip.ABI_VERSION == 11 and hip.lib().deva_hip_version() == 11  # additive: the version does not move
-    assert re.search(r'#define DEVA_HIP_ABI_VERSION 11\b', header)
+    header = abi_util.inference_entry_points(NAMES, returns='int')
     assert 'box_nms_xyxy' in ops.__all__ and 'box_mask_select' in ops.__all__
     assert len(hip.SIGNATURES) == 80
     for ref in ('grounding_dino.py:101-115', 'grounding_dino.py:112'):

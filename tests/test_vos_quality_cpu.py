@@ -1,7 +1,7 @@
 """Scoring a DAVIS-style run without a GPU: libdeva_vos_metrics.so on its ABI, its argument errors, its radius rule and its
 launch plan; the host arithmetic of J, F and the sequence statistics (rule R6 of include/deva_vos_metrics.h) on records
 written by hand; `deva.inference.vos_quality` on the CPU contract of the counts (tests/emu_vos.py, the numpy statement of
-tests/vos_case.py); the kernels' static resources; the HIP-free checks under the host sanitizers as a stand-alone program."""
+tests/vos_case.py); the kernels' static resources.  (The HIP-free checks under the host sanitizers: tests/test_plan_sanitize_cpu.py.)"""
 import ctypes
 import os
 import re
@@ -13,6 +13,7 @@ import pytest
 import torch
 from PIL import Image
 
+import abi_util
 import emu_vos as EV
 import vos_case as VC
 
@@ -21,7 +22,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, 'include', 'deva_vos_metrics.h')
 CSRC = os.path.join(ROOT, 'tracking-anything-with-deva_amd', 'csrc', 'vos_metrics')
 HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-CLANG = os.environ.get('DEVA_HOST_CXX', '/opt/rocm/llvm/bin/clang++')
 WANT = ['deva_vos_boundary_counts', 'deva_vos_boundary_plan', 'deva_vos_boundary_radius', 'deva_vos_boundary_scratch_bytes',
         'deva_vos_last_error', 'deva_vos_version']
 
@@ -33,29 +33,14 @@ def emu(monkeypatch):
 
 def _built():
     from deva.hip import vos_metrics
-    if not os.path.exists(vos_metrics.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return vos_metrics
-
-
-def _declared(header):
-    text = open(header).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    text = re.sub(r'//[^\n]*', '', text)
-    return sorted(set(re.findall(r'\b(deva_[a-z0-9_]+)\s*\(', text)))
-
-
-def _nm(lib_path):
-    out = subprocess.run(['nm', '-D', '--defined-only', lib_path], capture_output=True, text=True, check=True).stdout
-    return sorted(set(re.findall(r'\bT (deva_[a-z0-9_]+)$', out, flags=re.M))), set(re.findall(r'\b[TDBW] (\S+)$', out, flags=re.M))
+    return abi_util.built(vos_metrics)
 
 
 # ------------------------------------------------------------------------------------------ ABI
 def test_exports_header_and_binding_are_one_list():
     vm = _built()
-    exported, _ = _nm(vm.LIB_PATH)
-    assert exported == _declared(HEADER) == sorted(vm.SIGNATURES) == WANT
+    exported, _ = abi_util.exported(vm.LIB_PATH)
+    assert exported == abi_util.declared(HEADER) == sorted(vm.SIGNATURES) == WANT
     header = open(HEADER).read()
     assert re.search(r'#define DEVA_VOS_ABI_VERSION 1\b', header)
     assert vm.ABI_VERSION == 1 and vm.lib().deva_vos_version() == 1
@@ -71,10 +56,10 @@ def test_no_symbol_is_shared_with_the_other_two_libraries():
     from deva import hip
     from deva.hip import metrics
     vm = _built()
-    exported, mine = _nm(vm.LIB_PATH)
+    exported, mine = abi_util.exported(vm.LIB_PATH)
     assert all(name.startswith('deva_vos_') for name in exported)
     for other in (hip.LIB_PATH, metrics.LIB_PATH):
-        theirs_exported, theirs = _nm(other)
+        theirs_exported, theirs = abi_util.exported(other)
         assert not any(n.startswith('deva_vos') for n in theirs_exported)
         shared = {s for s in mine & theirs if 'deva' in s}
         assert not shared, (other, shared)
@@ -488,17 +473,3 @@ def test_no_kernel_spills_or_uses_scratch(src, tmp_path):
         assert r.get('VGPRs Spill', 0) == 0, (name, r)  # (SGPR spills go to VGPR lanes, not to memory)
         assert r.get('LDS Size', 0) <= 160 * 1024, (name, r)
         assert r['Occupancy'] >= 4, (name, r)            # the launches are sized for 8 workgroups of 4 waves per CU
-
-
-# ------------------------------------------------------------------------------------------ the host code under sanitizers
-def test_plan_and_checks_under_host_sanitizers(tmp_path):
-    """tests/vos_plan_sanitize_main.cpp: a stand-alone program; nothing is loaded into Python and no GPU is involved"""
-    exe = tmp_path / 'vos_plan_sanitize'
-    subprocess.run([CLANG, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                    '-I', os.path.join(ROOT, 'include'), '-I', CSRC, os.path.join(CSRC, 'boundary_plan.cpp'),
-                    os.path.join(ROOT, 'tests', 'vos_plan_sanitize_main.cpp'), '-o', str(exe)], check=True)
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
-    print(run.stdout, run.stderr[-4000:])
-    assert run.returncode == 0, run.stderr[-4000:]
-    checks, refused, failures = (int(v) for v in re.findall(r'\d+', run.stdout))
-    assert checks > 100000 and 0 < refused < checks and failures == 0

@@ -8,8 +8,6 @@
 
 namespace deva {
 
-static int64_t round256(int64_t v) { return (v + 255) / 256 * 256; }
-
 bool detection_sizes_ok(int n, int h0, int w0, int oh, int ow) {
   return n >= 0 && n <= kDetMaxMasks && h0 > 0 && w0 > 0 && oh > 0 && ow > 0 && (int64_t)h0 * w0 < (1ll << 31) &&
          (int64_t)oh * ow < (1ll << 31);
@@ -20,19 +18,19 @@ DetectionPlan detection_plan(int n, int h0, int w0, int oh, int ow) {
   const int64_t src = (int64_t)h0 * w0, dst = (int64_t)oh * ow;
   const int64_t most = src > dst ? src : dst;
   p.chunks = (int)((most + kDetChunk - 1) / kDetChunk);
-  const int64_t part = round256((int64_t)n * p.chunks * 4), per_mask = round256((int64_t)n * 4);
-  int64_t at = 0;
-  p.off_part_area = at, at += part;
-  p.off_part_orig = at, at += part;
-  p.off_part_src = at, at += part;
-  p.off_area = at, at += per_mask;
-  p.off_orig = at, at += per_mask;
-  p.off_src = at, at += per_mask;
-  p.off_mult = at, at += per_mask;
-  p.off_stats = at, at += round256((int64_t)(n + 1) * 8);
-  p.off_lut = at, at += round256((int64_t)(n + 1) * 4);
-  p.off_plane = at, at += round256(dst * 2);
-  p.bytes = at;
+  const int64_t part = (int64_t)n * p.chunks * 4, per_mask = (int64_t)n * 4;
+  ScratchLayout s;
+  p.off_part_area = s.take(part);
+  p.off_part_orig = s.take(part);
+  p.off_part_src = s.take(part);
+  p.off_area = s.take(per_mask);
+  p.off_orig = s.take(per_mask);
+  p.off_src = s.take(per_mask);
+  p.off_mult = s.take(per_mask);
+  p.off_stats = s.take((int64_t)(n + 1) * 8);
+  p.off_lut = s.take((int64_t)(n + 1) * 4);
+  p.off_plane = s.take(dst * 2);
+  p.bytes = s.at;
   return p;
 }
 
@@ -52,7 +50,7 @@ int detection_check(const void* masks, int n, int h0, int w0, int oh, int ow, in
   DEVA_REQUIRE(records, "%s: null record table", what);
   DEVA_REQUIRE(policy != DET_SUPPRESS_SMALL || !isnan(overlap_threshold), "%s: the overlap threshold is not a number", what);
   const int64_t need = detection_plan(n, h0, w0, oh, ow).bytes;
-  DEVA_REQUIRE(scratch && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 && scratch_bytes >= need,
+  DEVA_REQUIRE(scratch_ok(scratch, scratch_bytes, need),
                "%s: scratch of %lld bytes (16-byte aligned), deva_detection_scratch asks for %lld", what,
                (long long)(scratch ? scratch_bytes : 0), (long long)need);
   return 0;

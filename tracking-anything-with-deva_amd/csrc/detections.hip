@@ -372,7 +372,7 @@ extern "C" int deva_detection_assemble(const uint8_t* masks, int n_masks, int he
 
   const bool equal = out_height == height && out_width == width;
   const int mode = !equal ? DET_RESIZE
-                          : (dst % 16 == 0 && reinterpret_cast<uintptr_t>(masks) % 16 == 0 ? DET_VEC16 : DET_BYTES);
+                          : (dst % 16 == 0 && aligned(masks, 16) ? DET_VEC16 : DET_BYTES);
   const bool text = policy == DET_TEXT;
   const dim3 t(256), area_grid((unsigned)p.chunks, (unsigned)n_masks);
   int64_t blocks = ceil_div(mode == DET_VEC16 ? dst / 16 : dst, 256);
@@ -391,7 +391,7 @@ extern "C" int deva_detection_assemble(const uint8_t* masks, int n_masks, int he
   else DEVA_DET_LAUNCH(DET_RESIZE);
 #undef DEVA_DET_LAUNCH
   hipLaunchKernelGGL(det_table_kernel, dim3(1), dim3(256), 0, s, a);
-  const bool vec = dst % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+  const bool vec = dst % 4 == 0 && aligned(out, 16);
   int64_t paint_blocks = ceil_div(vec ? dst / 4 : dst, 256);
   if (paint_blocks > 2048) paint_blocks = 2048;
   if (vec) hipLaunchKernelGGL((det_paint_kernel<true>), dim3((unsigned)paint_blocks), t, 0, s, a);

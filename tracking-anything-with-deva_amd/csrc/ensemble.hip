@@ -265,7 +265,7 @@ extern "C" int deva_scores_u8(const deva_ensemble_variant* variant, int out_heig
   const int64_t blocks = ceil_div((int64_t)out_height * ((out_width + 3) / 4), 256);
   DEVA_REQUIRE(blocks < (1ll << 31), "deva_scores_u8: output too large");
   const dim3 grid((unsigned)blocks, (unsigned)(variant->channels < 65535 ? variant->channels : 65535));
-  if (out_width % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0)
+  if (out_width % 4 == 0 && aligned(out, 4))
     hipLaunchKernelGGL(scores_u8_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, v, variant->channels,
                        out_height, out_width, out);
   else
@@ -296,7 +296,7 @@ extern "C" int deva_ensemble_index_mask(const deva_ensemble_variant* variants, i
   a.out = out;
   const int64_t blocks = ceil_div((int64_t)out_height * ((out_width + 1) / 2), 256);
   DEVA_REQUIRE(blocks < (1ll << 31), "deva_ensemble_index_mask: output too large");
-  const bool vec = out_width % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+  const bool vec = out_width % 2 == 0 && aligned(out, 16);
   const bool quant = quantize != 0;
   const unsigned b = (unsigned)blocks;
   hipStream_t s = (hipStream_t)stream;

@@ -376,7 +376,6 @@ extern "C" int deva_frame_result(const float* prob, int channels, int height, in
   if (stats)
     hipLaunchKernelGGL(stats_init_kernel, dim3((unsigned)ceil_div((int64_t)channels * 5, 256)), dim3(256), 0, s, stats,
                        channels);
-  auto aligned = [](const void* p, uintptr_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; };
   const bool vec = out_width % 4 == 0 && aligned(index, 8) && aligned(labels, 16) && aligned(gray, 4) &&
                    aligned(color, 4) && aligned(blend, 4) && (!blend || aligned(image, 4));
   const int mode = !stats ? STATS_NONE : (channels <= kStatsLdsChannels ? STATS_LDS : STATS_GLOBAL);
@@ -409,7 +408,7 @@ static int rle_args(const char* what, int oh, int ow, int channels, const void* 
   DEVA_REQUIRE(oh > 0 && ow > 0 && channels > 0 && scratch, "%s: bad args", what);
   DEVA_REQUIRE(channels <= kRleMaxChannels, "%s: at most %d channels (got %d)", what, kRleMaxChannels, channels);
   DEVA_REQUIRE((int64_t)oh * ow < (1ll << 30), "%s: frame of 2^30 pixels or more", what);
-  DEVA_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 4 == 0 && scratch_bytes >= rle_plan(oh, ow, channels).bytes,
+  DEVA_REQUIRE(aligned(scratch, 4) && scratch_bytes >= rle_plan(oh, ow, channels).bytes,
                "%s: scratch of %lld bytes, deva_mask_rle_scratch asks for %lld", what, (long long)scratch_bytes,
                (long long)rle_plan(oh, ow, channels).bytes);
   return 0;

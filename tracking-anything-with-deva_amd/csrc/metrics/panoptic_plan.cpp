@@ -1,20 +1,9 @@
 // Argument checks and launch decision of the joint count (see panoptic_plan.h), and the library's host-only entry points.
 #include "panoptic_plan.h"
 
-#include <stdarg.h>
-#include <stdio.h>
-
 namespace deva_metrics {
 
-static thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
+HOST_ARGS_DEFINE_ERROR_TEXT()
 const char* last_error() { return g_err; }
 
 int encoding_bytes(int encoding) {
@@ -46,11 +35,6 @@ int panoptic_plan(const char* what, int height, int width, int n_gt, int n_pred,
   return 0;
 }
 
-static bool overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && a_bytes > 0 && b_bytes > 0 && a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
-}
-
 int panoptic_counts_check(const void* gt, int gt_encoding, const void* gt_ids, int n_gt, const void* pred, int pred_encoding,
                           const void* pred_ids, int n_pred, const void* pred_lut, int channels, int height, int width,
                           const void* counts, deva_metrics_plan* plan) {
@@ -62,24 +46,24 @@ int panoptic_counts_check(const void* gt, int gt_encoding, const void* gt_ids, i
   deva_metrics_plan local;
   if (int rc = panoptic_plan(what, height, width, n_gt, n_pred, plan ? plan : &local)) return rc;
   const bool fast = pred_encoding == DEVA_METRICS_INDEX16;
-  DEVA_METRICS_REQUIRE(gt && reinterpret_cast<uintptr_t>(gt) % 16 == 0, "%s: null or misaligned ground-truth plane", what);
-  DEVA_METRICS_REQUIRE(pred && reinterpret_cast<uintptr_t>(pred) % 16 == 0, "%s: null or misaligned predicted plane", what);
-  DEVA_METRICS_REQUIRE((gt_ids || n_gt == 0) && reinterpret_cast<uintptr_t>(gt_ids) % 4 == 0,
+  DEVA_METRICS_REQUIRE(gt && aligned(gt, 16), "%s: null or misaligned ground-truth plane", what);
+  DEVA_METRICS_REQUIRE(pred && aligned(pred, 16), "%s: null or misaligned predicted plane", what);
+  DEVA_METRICS_REQUIRE((gt_ids || n_gt == 0) && aligned(gt_ids, 4),
                        "%s: null or misaligned ground-truth id table", what);
-  DEVA_METRICS_REQUIRE(fast || ((pred_ids || n_pred == 0) && reinterpret_cast<uintptr_t>(pred_ids) % 4 == 0),
+  DEVA_METRICS_REQUIRE(fast || ((pred_ids || n_pred == 0) && aligned(pred_ids, 4)),
                        "%s: null or misaligned predicted id table", what);
   if (fast) {
     DEVA_METRICS_REQUIRE(channels >= 1 && channels <= 32767, "%s: 1 to 32767 channels (got %d)", what, channels);
-    DEVA_METRICS_REQUIRE(pred_lut && reinterpret_cast<uintptr_t>(pred_lut) % 2 == 0, "%s: null or misaligned channel table", what);
+    DEVA_METRICS_REQUIRE(pred_lut && aligned(pred_lut, 2), "%s: null or misaligned channel table", what);
   }
-  DEVA_METRICS_REQUIRE(counts && reinterpret_cast<uintptr_t>(counts) % 4 == 0, "%s: null or misaligned counts", what);
+  DEVA_METRICS_REQUIRE(counts && aligned(counts, 4), "%s: null or misaligned counts", what);
   const int64_t pixels = (int64_t)height * width;
   const int64_t out_bytes = 4ll * (n_gt + 2) * (n_pred + 2);
-  const bool clash = overlap(counts, out_bytes, gt, pixels * encoding_bytes(gt_encoding)) ||
-                     overlap(counts, out_bytes, pred, pixels * encoding_bytes(pred_encoding)) ||
-                     overlap(counts, out_bytes, gt_ids, 4ll * n_gt) ||
-                     (!fast && overlap(counts, out_bytes, pred_ids, 4ll * n_pred)) ||
-                     (fast && overlap(counts, out_bytes, pred_lut, 2ll * channels));
+  const bool clash = overlaps(counts, out_bytes, gt, pixels * encoding_bytes(gt_encoding)) ||
+                     overlaps(counts, out_bytes, pred, pixels * encoding_bytes(pred_encoding)) ||
+                     overlaps(counts, out_bytes, gt_ids, 4ll * n_gt) ||
+                     (!fast && overlaps(counts, out_bytes, pred_ids, 4ll * n_pred)) ||
+                     (fast && overlaps(counts, out_bytes, pred_lut, 2ll * channels));
   DEVA_METRICS_REQUIRE(!clash, "%s: counts overlaps an input", what);
   return 0;
 }

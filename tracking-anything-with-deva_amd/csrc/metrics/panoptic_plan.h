@@ -4,9 +4,11 @@
 #pragma once
 #include <stdint.h>
 
+#include "../host_args.h"
 #include "deva_metrics.h"
 
 namespace deva_metrics {
+using namespace host_args;
 
 constexpr int kBlock = 256;            // lanes of a workgroup
 constexpr int kMaxGrid = 2048;         // workgroups of a launch: 8 per CU; a larger plane is walked in a grid-stride loop
@@ -15,13 +17,7 @@ constexpr int64_t kMaxPixels = 1ll << 30;
 void set_error(const char* fmt, ...);  // panoptic_plan.cpp; text behind deva_metrics_last_error()
 const char* last_error();
 
-#define DEVA_METRICS_REQUIRE(cond, ...)     \
-  do {                                      \
-    if (!(cond)) {                          \
-      deva_metrics::set_error(__VA_ARGS__); \
-      return 2;                             \
-    }                                       \
-  } while (0)
+#define DEVA_METRICS_REQUIRE(cond, ...) HOST_ARGS_REQUIRE(deva_metrics::set_error, cond, __VA_ARGS__)
 
 // bytes of one pixel of a plane, 0 for an unknown encoding
 int encoding_bytes(int encoding);

@@ -8,8 +8,6 @@
 
 namespace deva {
 
-static int64_t round256(int64_t v) { return (v + 255) / 256 * 256; }
-
 bool prompt_size_ok(int height, int width) {
   return height >= kPromptScale && width >= kPromptScale && height <= kPromptMaxSide && width <= kPromptMaxSide &&
          (int64_t)height * width <= kPromptMaxPixels;
@@ -20,10 +18,10 @@ bool prompt_points_ok(int points) { return points >= 1 && points <= kPromptMaxPo
 PromptPlan prompt_plan(int height, int width) {
   PromptPlan p;
   p.low_h = height / kPromptScale, p.low_w = width / kPromptScale;
-  int64_t at = 0;
-  p.off_rows = at, at += round256((int64_t)height * p.low_w * 4);
-  p.off_low = at, at += round256((int64_t)p.low_h * p.low_w * 4);
-  p.bytes = at;
+  ScratchLayout s;
+  p.off_rows = s.take((int64_t)height * p.low_w * 4);
+  p.off_low = s.take((int64_t)p.low_h * p.low_w * 4);
+  p.bytes = s.at;
   return p;
 }
 
@@ -40,13 +38,13 @@ int prompt_points_check(const void* mask, int mask_elem_bytes, int height, int w
   DEVA_REQUIRE(points >= 1, "%s: at least one point (got %d)", what, points);
   DEVA_REQUIRE(points <= kPromptMaxPoints, "%s: at most %d points (got %d)", what, kPromptMaxPoints, points);
   DEVA_REQUIRE(!isnan(threshold), "%s: the threshold is not a number", what);
-  DEVA_REQUIRE(mask && reinterpret_cast<uintptr_t>(mask) % mask_elem_bytes == 0, "%s: null or misaligned mask", what);
-  DEVA_REQUIRE(points_xy && reinterpret_cast<uintptr_t>(points_xy) % 4 == 0, "%s: null or misaligned points", what);
-  DEVA_REQUIRE(out_points && reinterpret_cast<uintptr_t>(out_points) % 4 == 0, "%s: null or misaligned kept points", what);
-  DEVA_REQUIRE(out_labels && reinterpret_cast<uintptr_t>(out_labels) % 4 == 0, "%s: null or misaligned labels", what);
-  DEVA_REQUIRE(out_count && reinterpret_cast<uintptr_t>(out_count) % 4 == 0, "%s: null or misaligned count", what);
+  DEVA_REQUIRE(mask && aligned(mask, mask_elem_bytes), "%s: null or misaligned mask", what);
+  DEVA_REQUIRE(points_xy && aligned(points_xy, 4), "%s: null or misaligned points", what);
+  DEVA_REQUIRE(out_points && aligned(out_points, 4), "%s: null or misaligned kept points", what);
+  DEVA_REQUIRE(out_labels && aligned(out_labels, 4), "%s: null or misaligned labels", what);
+  DEVA_REQUIRE(out_count && aligned(out_count, 4), "%s: null or misaligned count", what);
   const int64_t need = prompt_plan(height, width).bytes;
-  DEVA_REQUIRE(scratch && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 && scratch_bytes >= need,
+  DEVA_REQUIRE(scratch_ok(scratch, scratch_bytes, need),
                "%s: scratch of %lld bytes (16-byte aligned), deva_prompt_scratch asks for %lld", what,
                (long long)(scratch ? scratch_bytes : 0), (long long)need);
   return 0;

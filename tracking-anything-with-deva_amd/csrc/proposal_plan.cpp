@@ -8,8 +8,6 @@
 
 namespace deva {
 
-static int64_t round256(int64_t v) { return (v + 255) / 256 * 256; }
-
 bool proposal_capacity_ok(int capacity) { return capacity >= 1 && capacity <= kPropMaxMasks; }
 
 int proposal_chunks(int height, int width) {
@@ -19,16 +17,16 @@ int proposal_chunks(int height, int width) {
 ProposalPlan proposal_plan(int capacity) {
   ProposalPlan p;
   p.words = (capacity + 63) / 64;
-  int64_t at = 0;
-  p.off_stats = at, at += round256((int64_t)kPropBatch * kPropStat * 4);
-  p.off_slots = at, at += round256((int64_t)kPropBatch * 4);
-  p.off_count = at, at += 256;
-  p.off_table = at, at += round256((int64_t)capacity * kPropRow * 4);
-  p.off_order = at, at += round256((int64_t)capacity * 4);
-  p.off_keep = at, at += round256((int64_t)capacity * 4);
-  p.off_nkeep = at, at += 256;
-  p.off_matrix = at, at += round256((int64_t)capacity * p.words * 8);
-  p.bytes = at;
+  ScratchLayout s;
+  p.off_stats = s.take((int64_t)kPropBatch * kPropStat * 4);
+  p.off_slots = s.take((int64_t)kPropBatch * 4);
+  p.off_count = s.take(256);
+  p.off_table = s.take((int64_t)capacity * kPropRow * 4);
+  p.off_order = s.take((int64_t)capacity * 4);
+  p.off_keep = s.take((int64_t)capacity * 4);
+  p.off_nkeep = s.take(256);
+  p.off_matrix = s.take((int64_t)capacity * p.words * 8);
+  p.bytes = s.at;
   return p;
 }
 
@@ -36,7 +34,7 @@ static int scratch_check(const char* what, int capacity, const void* scratch, in
   DEVA_REQUIRE(capacity >= 1, "%s: a capacity of at least one mask (got %d)", what, capacity);
   DEVA_REQUIRE(capacity <= kPropMaxMasks, "%s: at most %d masks (got %d)", what, kPropMaxMasks, capacity);
   const int64_t need = proposal_plan(capacity).bytes;
-  DEVA_REQUIRE(scratch && reinterpret_cast<uintptr_t>(scratch) % 16 == 0 && scratch_bytes >= need,
+  DEVA_REQUIRE(scratch_ok(scratch, scratch_bytes, need),
                "%s: scratch of %lld bytes (16-byte aligned), deva_proposal_scratch asks for %lld", what,
                (long long)(scratch ? scratch_bytes : 0), (long long)need);
   return 0;
@@ -64,7 +62,7 @@ int proposal_batch_check(const void* logits, const void* iou_preds, int batch, i
   if (int e = scratch_check(what, capacity, scratch, scratch_bytes)) return e;
   DEVA_REQUIRE(arena, "%s: null arena", what);
   if (batch == 0) return 0;  // (nothing else is read)
-  DEVA_REQUIRE(logits && reinterpret_cast<uintptr_t>(logits) % 4 == 0, "%s: null or misaligned logits", what);
+  DEVA_REQUIRE(logits && aligned(logits, 4), "%s: null or misaligned logits", what);
   DEVA_REQUIRE(iou_preds, "%s: null predicted IoUs", what);
   return 0;
 }
@@ -73,7 +71,7 @@ int proposal_finish_check(int capacity, double box_nms_thresh, const void* scrat
   const char* what = "deva_proposal_finish";
   if (int e = scratch_check(what, capacity, scratch, scratch_bytes)) return e;
   DEVA_REQUIRE(!isnan(box_nms_thresh), "%s: the NMS threshold is not a number", what);
-  DEVA_REQUIRE(result && reinterpret_cast<uintptr_t>(result) % 4 == 0, "%s: null or misaligned result table", what);
+  DEVA_REQUIRE(result && aligned(result, 4), "%s: null or misaligned result table", what);
   return 0;
 }
 
@@ -95,11 +93,11 @@ int box_nms_check(const void* boxes, const void* scores, int m, double box_nms_t
   DEVA_REQUIRE(m >= 0, "%s: negative number of boxes (%d)", what, m);
   DEVA_REQUIRE(m <= kPropMaxMasks, "%s: at most %d boxes (got %d)", what, kPropMaxMasks, m);
   DEVA_REQUIRE(!isnan(box_nms_thresh), "%s: the NMS threshold is not a number", what);
-  DEVA_REQUIRE(n_keep && reinterpret_cast<uintptr_t>(n_keep) % 4 == 0, "%s: null or misaligned keep count", what);
+  DEVA_REQUIRE(n_keep && aligned(n_keep, 4), "%s: null or misaligned keep count", what);
   if (m == 0) return 0;  // (a count of 0: nothing else is touched)
-  DEVA_REQUIRE(boxes && reinterpret_cast<uintptr_t>(boxes) % 4 == 0, "%s: null or misaligned boxes", what);
-  DEVA_REQUIRE(scores && reinterpret_cast<uintptr_t>(scores) % 4 == 0, "%s: null or misaligned scores", what);
-  DEVA_REQUIRE(keep && reinterpret_cast<uintptr_t>(keep) % 4 == 0, "%s: null or misaligned keep list", what);
+  DEVA_REQUIRE(boxes && aligned(boxes, 4), "%s: null or misaligned boxes", what);
+  DEVA_REQUIRE(scores && aligned(scores, 4), "%s: null or misaligned scores", what);
+  DEVA_REQUIRE(keep && aligned(keep, 4), "%s: null or misaligned keep list", what);
   return scratch_check(what, m, scratch, scratch_bytes);
 }
 

@@ -1,17 +1,10 @@
 // Error channel + version of libdeva_hip.so, and the matrix-pipe probe.
-#include <stdarg.h>
 #include <string.h>
 
 #include "common.h"
 
 namespace deva {
-static thread_local char g_err[512] = "";
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
+HOST_ARGS_DEFINE_ERROR_TEXT()
 }  // namespace deva
 
 extern "C" int deva_hip_version(void) { return DEVA_HIP_ABI_VERSION; }

@@ -3,20 +3,10 @@
 #include "boundary_plan.h"
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 namespace deva_vos {
 
-static thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
+HOST_ARGS_DEFINE_ERROR_TEXT()
 const char* last_error() { return g_err; }
 
 int encoding_bytes(int encoding) {
@@ -75,11 +65,6 @@ int boundary_plan(const char* what, int height, int width, int n_objects, int ra
   return 0;
 }
 
-static bool overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && a_bytes > 0 && b_bytes > 0 && a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
-}
-
 int boundary_counts_check(const void* gt, int gt_encoding, const void* pred, int pred_encoding, const void* ids, int n_objects,
                           const void* pred_lut, int channels, int height, int width, int radius, const void* scratch,
                           int64_t scratch_bytes, const void* counts, deva_vos_plan* plan) {
@@ -95,29 +80,29 @@ int boundary_counts_check(const void* gt, int gt_encoding, const void* pred, int
   const bool binary = ((gt_encoding | pred_encoding) & DEVA_VOS_BINARY) != 0;
   DEVA_VOS_REQUIRE(!binary || n_objects == 1, "%s: BINARY planes hold one object (got %d)", what, n_objects);
   const bool fast = pred_plain == DEVA_VOS_INDEX16;
-  DEVA_VOS_REQUIRE(gt && reinterpret_cast<uintptr_t>(gt) % 16 == 0, "%s: null or misaligned ground-truth plane", what);
-  DEVA_VOS_REQUIRE(pred && reinterpret_cast<uintptr_t>(pred) % 16 == 0, "%s: null or misaligned predicted plane", what);
-  DEVA_VOS_REQUIRE(ids && reinterpret_cast<uintptr_t>(ids) % 4 == 0, "%s: null or misaligned id table", what);
+  DEVA_VOS_REQUIRE(gt && aligned(gt, 16), "%s: null or misaligned ground-truth plane", what);
+  DEVA_VOS_REQUIRE(pred && aligned(pred, 16), "%s: null or misaligned predicted plane", what);
+  DEVA_VOS_REQUIRE(ids && aligned(ids, 4), "%s: null or misaligned id table", what);
   if (fast) {
     DEVA_VOS_REQUIRE(channels >= 1 && channels <= 32767, "%s: 1 to 32767 channels (got %d)", what, channels);
-    DEVA_VOS_REQUIRE(pred_lut && reinterpret_cast<uintptr_t>(pred_lut) % 2 == 0, "%s: null or misaligned channel table", what);
+    DEVA_VOS_REQUIRE(pred_lut && aligned(pred_lut, 2), "%s: null or misaligned channel table", what);
   }
-  DEVA_VOS_REQUIRE(scratch && reinterpret_cast<uintptr_t>(scratch) % 16 == 0, "%s: null or misaligned scratch", what);
+  DEVA_VOS_REQUIRE(scratch && aligned(scratch, 16), "%s: null or misaligned scratch", what);
   DEVA_VOS_REQUIRE(scratch_bytes >= plan->scratch_bytes, "%s: the scratch holds %lld bytes, %lld are needed", what,
                    (long long)scratch_bytes, (long long)plan->scratch_bytes);
-  DEVA_VOS_REQUIRE(counts && reinterpret_cast<uintptr_t>(counts) % 4 == 0, "%s: null or misaligned counts", what);
+  DEVA_VOS_REQUIRE(counts && aligned(counts, 4), "%s: null or misaligned counts", what);
   const int64_t pixels = (int64_t)height * width;
   const int64_t out_bytes = 4ll * DEVA_VOS_FIELDS * n_objects;
-  const bool clash = overlap(counts, out_bytes, gt, pixels * encoding_bytes(gt_encoding)) ||
-                     overlap(counts, out_bytes, pred, pixels * encoding_bytes(pred_encoding)) ||
-                     overlap(counts, out_bytes, ids, 4ll * n_objects) ||
-                     (fast && overlap(counts, out_bytes, pred_lut, 2ll * channels)) ||
-                     overlap(counts, out_bytes, scratch, plan->scratch_bytes);
+  const bool clash = overlaps(counts, out_bytes, gt, pixels * encoding_bytes(gt_encoding)) ||
+                     overlaps(counts, out_bytes, pred, pixels * encoding_bytes(pred_encoding)) ||
+                     overlaps(counts, out_bytes, ids, 4ll * n_objects) ||
+                     (fast && overlaps(counts, out_bytes, pred_lut, 2ll * channels)) ||
+                     overlaps(counts, out_bytes, scratch, plan->scratch_bytes);
   DEVA_VOS_REQUIRE(!clash, "%s: counts overlaps an input", what);
-  const bool scribble = overlap(scratch, plan->scratch_bytes, gt, pixels * encoding_bytes(gt_encoding)) ||
-                        overlap(scratch, plan->scratch_bytes, pred, pixels * encoding_bytes(pred_encoding)) ||
-                        overlap(scratch, plan->scratch_bytes, ids, 4ll * n_objects) ||
-                        (fast && overlap(scratch, plan->scratch_bytes, pred_lut, 2ll * channels));
+  const bool scribble = overlaps(scratch, plan->scratch_bytes, gt, pixels * encoding_bytes(gt_encoding)) ||
+                        overlaps(scratch, plan->scratch_bytes, pred, pixels * encoding_bytes(pred_encoding)) ||
+                        overlaps(scratch, plan->scratch_bytes, ids, 4ll * n_objects) ||
+                        (fast && overlaps(scratch, plan->scratch_bytes, pred_lut, 2ll * channels));
   DEVA_VOS_REQUIRE(!scribble, "%s: the scratch overlaps an input", what);
   return 0;
 }

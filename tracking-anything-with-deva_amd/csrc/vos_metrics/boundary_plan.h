@@ -4,9 +4,11 @@
 #pragma once
 #include <stdint.h>
 
+#include "../host_args.h"
 #include "deva_vos_metrics.h"
 
 namespace deva_vos {
+using namespace host_args;
 
 constexpr int kBlock = 256;     // lanes of a workgroup: 4 waves
 constexpr int kWave = 64;
@@ -18,13 +20,7 @@ constexpr int kWordBytes = 16;  // the two boundary words of a pixel, side by si
 void set_error(const char* fmt, ...);  // boundary_plan.cpp; text behind deva_vos_last_error()
 const char* last_error();
 
-#define DEVA_VOS_REQUIRE(cond, ...)     \
-  do {                                  \
-    if (!(cond)) {                      \
-      deva_vos::set_error(__VA_ARGS__); \
-      return 2;                         \
-    }                                   \
-  } while (0)
+#define DEVA_VOS_REQUIRE(cond, ...) HOST_ARGS_REQUIRE(deva_vos::set_error, cond, __VA_ARGS__)
 
 // bytes of one pixel of a plane (the BINARY flag is ignored), 0 for an unknown encoding
 int encoding_bytes(int encoding);

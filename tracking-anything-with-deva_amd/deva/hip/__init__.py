@@ -8,6 +8,8 @@ import ctypes
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
+from . import _native
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libdeva_hip.so')
 ABI_VERSION = 11
@@ -184,23 +186,9 @@ class DevaHipError(RuntimeError):
 
 def lib() -> ctypes.CDLL:
     """Load (once) and return the native library; raises if it has not been built."""
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(LIB_PATH):
-            raise DevaHipError(
-                f'{LIB_PATH} not found: the HIP kernels are not built. Run `python __graft_entry__.py` '
-                '(or `make -C tracking-anything-with-deva_amd/csrc`). There is no CPU fallback.')
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.deva_hip_version() != ABI_VERSION:
-            raise DevaHipError(f'libdeva_hip.so ABI {handle.deva_hip_version()} != binding {ABI_VERSION}')
-        _LIB = handle
-    return _LIB
+    return _LIB or _native.load(globals(), 'deva_hip_version', 'libdeva_hip.so', 'the HIP kernels')
 
 
 def check(code: int, what: str) -> None:
-    if code != 0:
-        raise DevaHipError(f'{what} failed: {lib().deva_hip_last_error().decode()}')
+    if code != 0:   # (tested here: the inference wrappers call this after every launch)
+        _native.check(globals(), code, what, 'deva_hip_last_error')

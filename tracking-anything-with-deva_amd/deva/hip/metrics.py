@@ -11,7 +11,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import DevaHipError
+from . import DevaHipError, _native, _planes
 from .ops import _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -45,26 +45,12 @@ _LIB = None
 
 def lib() -> ctypes.CDLL:
     """Load (once) and return the scoring library; raises if it has not been built."""
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(LIB_PATH):
-            raise DevaHipError(
-                f'{LIB_PATH} not found: the scoring kernels are not built. Run `python __graft_entry__.py` '
-                '(or `make -C tracking-anything-with-deva_amd/csrc`). There is no CPU fallback.')
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.deva_metrics_version() != ABI_VERSION:
-            raise DevaHipError(f'libdeva_metrics.so ABI {handle.deva_metrics_version()} != binding {ABI_VERSION}')
-        _LIB = handle
-    return _LIB
+    return _LIB or _native.load(globals(), 'deva_metrics_version', 'libdeva_metrics.so', 'the scoring kernels')
 
 
 def check(code: int, what: str) -> None:
-    if code != 0:
-        raise DevaHipError(f'{what} failed: {lib().deva_metrics_last_error().decode()}')
+    if code != 0:   # (tested here: the inference wrappers call this after every launch)
+        _native.check(globals(), code, what, 'deva_metrics_last_error')
 
 
 class PlanInfo(NamedTuple):
@@ -98,28 +84,11 @@ def id_table(ids, what: str = 'ids') -> np.ndarray:
 
 def _table(ids, device, what: str, validate: bool = True):
     """`ids` as given by the caller -> (device int32 tensor or None, n); a tensor or array is taken as the table itself
-    and must be strictly ascending and positive (the library cannot see that from the host, so it is checked here: for
-    a device tensor that is a copy to the host, which `validate=False` leaves out)"""
+    and must be strictly ascending and positive"""
     if ids is None:
         return None, 0
-    if not validate and isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous():
-        if ids.numel() > MAX_IDS:
-            raise DevaHipError(f'panoptic_counts: at most {MAX_IDS} {what} (got {ids.numel()})')
-        return (ids if ids.numel() else None), ids.numel()
-    if isinstance(ids, torch.Tensor) and ids.is_cuda:
-        host = ids.cpu().numpy()
-    else:
-        host = np.asarray(ids.numpy() if isinstance(ids, torch.Tensor) else ids)
-    host = host.reshape(-1).astype(np.int64)
-    if host.size > MAX_IDS:
-        raise DevaHipError(f'panoptic_counts: at most {MAX_IDS} {what} (got {host.size})')
-    if host.size and (host[0] < 1 or host[-1] > 2**31 - 1 or bool((np.diff(host) <= 0).any())):
-        raise DevaHipError(f'panoptic_counts: {what} must be distinct, ascending and in 1 .. 2^31 - 1')
-    if host.size == 0:
-        return None, 0
-    if isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous():
-        return ids, host.size
-    return torch.from_numpy(host.astype(np.int32)).to(device), host.size
+    return _planes.device_ids(ids, device, 'panoptic_counts', what, validate=validate, allow_empty=True, max_ids=MAX_IDS,
+                              trusted_must_be_contiguous=True)
 
 
 def _plane(t: torch.Tensor, name: str, allowed):
@@ -136,13 +105,6 @@ def _plane(t: torch.Tensor, name: str, allowed):
     if enc not in allowed:
         raise DevaHipError(f'panoptic_counts: {name} cannot be {t.dtype}')
     return t, enc, (int(t.shape[0]), int(t.shape[1]))
-
-
-def _device_plane(t: torch.Tensor, name: str) -> torch.Tensor:
-    if not t.is_cuda:
-        raise DevaHipError(f'panoptic_counts: {name} must live on the HIP device (got {t.device}); there is no CPU path')
-    t = t.contiguous()
-    return t.clone() if t.data_ptr() % 16 else t   # (a view into the middle of a buffer)
 
 
 def panoptic_counts(gt: torch.Tensor, gt_ids, pred: torch.Tensor, pred_ids=None, pred_lut: Optional[torch.Tensor] = None,
@@ -174,16 +136,13 @@ def panoptic_counts(gt: torch.Tensor, gt_ids, pred: torch.Tensor, pred_ids=None,
     else:
         pred_tab, n_pred = _table(pred_ids, device, 'pred_ids', validate)
     if fast:
-        if pred_lut.dim() != 1 or pred_lut.dtype != torch.uint16 or not 1 <= pred_lut.numel() <= 32767:
-            raise DevaHipError('panoptic_counts: pred_lut must be uint16 [channels], 1 to 32767 channels')
+        _planes.check_pred_lut(pred_lut, 'panoptic_counts')
     g, p = n_gt + 2, n_pred + 2
-    if out is not None and (out.dtype != torch.uint32 or tuple(out.shape) != (g, p)):
-        raise DevaHipError(f'panoptic_counts: `out` must be uint32 [{g},{p}]')
-    gt, pred = _device_plane(gt, 'gt'), _device_plane(pred, 'pred')
+    _planes.check_out(out, (g, p), 'panoptic_counts')
+    gt, pred = _planes.on_device(gt, 'gt', 'panoptic_counts'), _planes.on_device(pred, 'pred', 'panoptic_counts')
     if fast:
-        pred_lut = _device_plane(pred_lut, 'pred_lut')
-    if out is not None and not (out.is_cuda and out.is_contiguous()):
-        raise DevaHipError('panoptic_counts: `out` must be a contiguous tensor on the HIP device')
+        pred_lut = _planes.on_device(pred_lut, 'pred_lut', 'panoptic_counts')
+    _planes.check_out_on_device(out, 'panoptic_counts')
     counts = torch.empty((g, p), dtype=torch.uint32, device=device) if out is None else out
     check(lib().deva_metrics_panoptic_counts(
         gt.data_ptr(), gt_enc, None if gt_tab is None else gt_tab.data_ptr(), n_gt,

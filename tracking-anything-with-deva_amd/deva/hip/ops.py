@@ -1180,6 +1180,11 @@ def frame_result(prob: torch.Tensor, size: Optional[Tuple[int, int]] = None, lut
     return FrameProducts(**res)
 
 
+def _scratch_i32(nbytes: int, device) -> torch.Tensor:
+    """scratch of at least `nbytes` bytes for one call, as whole 16-byte groups of int32"""
+    return torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=device)
+
+
 def mask_rle(index: torch.Tensor, channels: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """int16 [OH,OW] channel-index plane (`frame_result(...).index`) -> (n, bounds): the COCO run boundaries of every
     channel c >= 1.  Positions are column-major (p = x*OH + y) and start after "no object"; bounds_c = the ascending p
@@ -1246,7 +1251,7 @@ def detection_assemble(masks: torch.Tensor, size: Optional[Tuple[int, int]] = No
     planes = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
     out = torch.empty((oh, ow), dtype=torch.int64, device=masks.device)
     records = torch.empty((n, len(DETECTION_RECORD)), dtype=torch.int32, device=masks.device)
-    scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=masks.device)
+    scratch = _scratch_i32(nbytes, masks.device)
     check(lib().deva_detection_assemble(_p(planes, torch.uint8, 'masks') if n else None, n, h, w, oh, ow,
                                         DETECTION_POLICIES.index(policy), float(overlap_threshold), int(bool(consistent_ids)),
                                         _p(scores, name='scores') if n else None,
@@ -1298,7 +1303,7 @@ def proposal_state(height: int, width: int, capacity: int, device, arena: Option
         raise DevaHipError(f'proposal_state: the arena must be a contiguous uint8 tensor of {capacity} x {height} x {width}')
     _p(arena, torch.uint8, 'arena')
     nbytes = lib().deva_proposal_scratch(capacity)
-    scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=device)
+    scratch = _scratch_i32(nbytes, device)
     result = torch.empty(4 + capacity * len(PROPOSAL_ROW), dtype=torch.int32, device=device)
     host = torch.empty(result.shape, dtype=torch.int32, pin_memory=True)
     return ProposalState(height, width, capacity, arena, scratch, nbytes, result, host)
@@ -1351,24 +1356,40 @@ def proposal_finish(state: ProposalState, box_nms_thresh: float) -> ProposalResu
                           on_device[:, 2].contiguous().view(torch.float32), rows[:, 3:7].contiguous(), rows[:, 0].contiguous())
 
 
+def _box_nms(what: str, boxes: torch.Tensor, dtype, scores: torch.Tensor, thresh: float, packed: Optional[torch.Tensor],
+             refuse_nan: bool) -> torch.Tensor:
+    """the body of `box_nms` (int32 boxes) and `box_nms_xyxy` (fp32 boxes, `packed`, a NaN threshold refused here)"""
+    kind = 'int32' if dtype == torch.int32 else 'fp32'
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise DevaHipError(f'{what}: {kind} [M,4] boxes expected (got {tuple(boxes.shape)})')
+    m = boxes.shape[0]
+    if tuple(scores.shape) != (m,):
+        raise DevaHipError(f'{what}: scores must be fp32 [{m}] (got {tuple(scores.shape)})')
+    if m > PROPOSAL_MAX_MASKS:
+        raise DevaHipError(f'{what}: at most {PROPOSAL_MAX_MASKS} boxes (got {m})')
+    if refuse_nan and float(thresh) != float(thresh):
+        raise DevaHipError(f'{what}: the NMS threshold is not a number')
+    bp, sp = _p(boxes, dtype, 'boxes'), _p(scores, name='scores')
+    if packed is None:
+        keep = torch.empty(m + 1, dtype=torch.int32, device=boxes.device)     # the count travels behind the list
+    elif _p(packed, torch.int32, 'packed') is None or packed.numel() != m + 1:
+        raise DevaHipError(f'{what}: `packed` must be int32 [{m + 1}]')
+    else:
+        keep = packed
+    nbytes = lib().deva_proposal_scratch(m) if m else 0
+    scratch = _scratch_i32(nbytes, boxes.device)
+    check(getattr(lib(), 'deva_' + what)(bp if m else None, sp if m else None, m, float(thresh), scratch.data_ptr() if m else None,
+                                         nbytes, keep.data_ptr(), keep.data_ptr() + 4 * m, _stream()), 'deva_' + what)
+    if packed is not None:
+        return packed
+    return keep[:int(keep[m])].clone()
+
+
 def box_nms(boxes: torch.Tensor, scores: torch.Tensor, box_nms_thresh: float) -> torch.Tensor:
     """int32 [M,4] boxes (x0, y0, x1, y1) and fp32 [M] scores on the device -> int32 [K] kept indices on the device, in
     keep order: rule 5 of the proposal filter's contract (torchvision's CPU arithmetic; descending score, among equal
     scores the lower index).  Reading K synchronises once."""
-    if boxes.dim() != 2 or boxes.shape[1] != 4:
-        raise DevaHipError(f'box_nms: int32 [M,4] boxes expected (got {tuple(boxes.shape)})')
-    m = boxes.shape[0]
-    if tuple(scores.shape) != (m,):
-        raise DevaHipError(f'box_nms: scores must be fp32 [{m}] (got {tuple(scores.shape)})')
-    if m > PROPOSAL_MAX_MASKS:
-        raise DevaHipError(f'box_nms: at most {PROPOSAL_MAX_MASKS} boxes (got {m})')
-    bp, sp = _p(boxes, torch.int32, 'boxes'), _p(scores, name='scores')
-    keep = torch.empty(m + 1, dtype=torch.int32, device=boxes.device)     # the count travels behind the list
-    nbytes = lib().deva_proposal_scratch(m) if m else 0
-    scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=boxes.device)
-    check(lib().deva_box_nms(bp if m else None, sp if m else None, m, float(box_nms_thresh), scratch.data_ptr() if m else None,
-                             nbytes, keep.data_ptr(), keep.data_ptr() + 4 * m, _stream()), 'deva_box_nms')
-    return keep[:int(keep[m])].clone()
+    return _box_nms('box_nms', boxes, torch.int32, scores, box_nms_thresh, None, False)
 
 
 # ------------------------------------------------------------------------------------------ box prompts
@@ -1382,30 +1403,7 @@ def box_nms_xyxy(boxes: torch.Tensor, scores: torch.Tensor, thresh: float, *,
     arithmetic; descending score, a NaN first, among equal scores the lower index).  Reading K synchronises once.
     `packed`: the caller's int32 [M + 1] device tensor that receives the list and, behind it, the count; nothing
     synchronises then and `packed` itself is returned (one host copy fetches both)."""
-    if boxes.dim() != 2 or boxes.shape[1] != 4:
-        raise DevaHipError(f'box_nms_xyxy: fp32 [M,4] boxes expected (got {tuple(boxes.shape)})')
-    m = boxes.shape[0]
-    if tuple(scores.shape) != (m,):
-        raise DevaHipError(f'box_nms_xyxy: scores must be fp32 [{m}] (got {tuple(scores.shape)})')
-    if m > PROPOSAL_MAX_MASKS:
-        raise DevaHipError(f'box_nms_xyxy: at most {PROPOSAL_MAX_MASKS} boxes (got {m})')
-    thresh = float(thresh)
-    if thresh != thresh:
-        raise DevaHipError('box_nms_xyxy: the NMS threshold is not a number')
-    bp, sp = _p(boxes, name='boxes'), _p(scores, name='scores')
-    if packed is None:
-        keep = torch.empty(m + 1, dtype=torch.int32, device=boxes.device)     # the count travels behind the list
-    elif _p(packed, torch.int32, 'packed') is None or packed.numel() != m + 1:
-        raise DevaHipError(f'box_nms_xyxy: `packed` must be int32 [{m + 1}]')
-    else:
-        keep = packed
-    nbytes = lib().deva_proposal_scratch(m) if m else 0
-    scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=boxes.device)
-    check(lib().deva_box_nms_xyxy(bp if m else None, sp if m else None, m, thresh, scratch.data_ptr() if m else None,
-                                  nbytes, keep.data_ptr(), keep.data_ptr() + 4 * m, _stream()), 'deva_box_nms_xyxy')
-    if packed is not None:
-        return packed
-    return keep[:int(keep[m])].clone()
+    return _box_nms('box_nms_xyxy', boxes, torch.float32, scores, thresh, packed, True)
 
 
 def box_mask_select(logits: torch.Tensor, scores: torch.Tensor, mask_threshold: float = 0.0,
@@ -1478,7 +1476,7 @@ def prompt_points(mask: torch.Tensor, points_xy: torch.Tensor, threshold: float 
     if nbytes < 0:
         raise DevaHipError(f'prompt_points: a mask of {h} x {w} with {n} points is not supported')
     if scratch is None:
-        scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=device)
+        scratch = _scratch_i32(nbytes, device)
     elif _p(scratch, torch.int32, 'scratch') % 16 or scratch.numel() * 4 < nbytes:
         raise DevaHipError(f'prompt_points: the scratch must be a 16-byte aligned int32 tensor of {nbytes} bytes')
     if packed is None:

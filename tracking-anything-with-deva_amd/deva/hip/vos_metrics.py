@@ -12,7 +12,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import DevaHipError
+from . import DevaHipError, _native, _planes
 from .ops import _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,26 +54,12 @@ _LIB = None
 
 def lib() -> ctypes.CDLL:
     """Load (once) and return the DAVIS scoring library; raises if it has not been built."""
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(LIB_PATH):
-            raise DevaHipError(
-                f'{LIB_PATH} not found: the DAVIS scoring kernels are not built. Run `python __graft_entry__.py` '
-                '(or `make -C tracking-anything-with-deva_amd/csrc`). There is no CPU fallback.')
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.deva_vos_version() != ABI_VERSION:
-            raise DevaHipError(f'libdeva_vos_metrics.so ABI {handle.deva_vos_version()} != binding {ABI_VERSION}')
-        _LIB = handle
-    return _LIB
+    return _LIB or _native.load(globals(), 'deva_vos_version', 'libdeva_vos_metrics.so', 'the DAVIS scoring kernels')
 
 
 def check(code: int, what: str) -> None:
-    if code != 0:
-        raise DevaHipError(f'{what} failed: {lib().deva_vos_last_error().decode()}')
+    if code != 0:   # (tested here: the inference wrappers call this after every launch)
+        _native.check(globals(), code, what, 'deva_vos_last_error')
 
 
 class PlanInfo(NamedTuple):
@@ -115,14 +101,7 @@ _PRED_ENC = {torch.uint8: U8, torch.int32: I32, torch.int64: I64, torch.int16: I
 
 def id_list(ids) -> np.ndarray:
     """`ids` as the caller gives them -> int32 [n], checked: distinct, ascending, in 1 .. 2^31 - 1, at least one"""
-    if isinstance(ids, torch.Tensor):
-        ids = ids.cpu().numpy()
-    a = np.asarray(list(ids) if not isinstance(ids, np.ndarray) else ids, dtype=np.int64).reshape(-1)
-    if a.size == 0:
-        raise DevaHipError('boundary_counts: at least one object id')
-    if a[0] < 1 or a[-1] > 2**31 - 1 or bool((np.diff(a) <= 0).any()):
-        raise DevaHipError('boundary_counts: ids must be distinct, ascending and in 1 .. 2^31 - 1')
-    return a.astype(np.int32)
+    return _planes.host_ids(ids, 'boundary_counts', 'ids', allow_empty=False)
 
 
 def _plane(t, name: str, encodings):
@@ -132,13 +111,6 @@ def _plane(t, name: str, encodings):
         raise DevaHipError(f'boundary_counts: {name} must be an [H,W] plane of {", ".join(str(d) for d in encodings)} '
                            f'(got {t.dtype} {tuple(t.shape)})')
     return encodings[t.dtype], (int(t.shape[0]), int(t.shape[1]))
-
-
-def _on_device(t: torch.Tensor, name: str, align: int = 16) -> torch.Tensor:
-    if not t.is_cuda:
-        raise DevaHipError(f'boundary_counts: {name} must live on the HIP device (got {t.device}); there is no CPU path')
-    t = t.contiguous()
-    return t.clone() if t.data_ptr() % align else t   # (a view into the middle of a buffer)
 
 
 def _sides(binary):
@@ -174,16 +146,11 @@ def boundary_counts(gt: torch.Tensor, pred: torch.Tensor, ids, *, bound_th: floa
     fast = pred_enc == INDEX16
     if fast != (pred_lut is not None):
         raise DevaHipError('boundary_counts: the int16 channel plane and pred_lut go together')
-    if fast and (pred_lut.dim() != 1 or pred_lut.dtype != torch.uint16 or not 1 <= pred_lut.numel() <= 32767):
-        raise DevaHipError('boundary_counts: pred_lut must be uint16 [channels], 1 to 32767 channels')
+    if fast:
+        _planes.check_pred_lut(pred_lut, 'boundary_counts')
     device = gt.device
-    if not validate and isinstance(ids, torch.Tensor) and ids.dtype == torch.int32 and ids.dim() == 1 and ids.numel() >= 1:
-        table, n = ids, ids.numel()
-    else:
-        host = id_list(ids)
-        n = host.size
-        table = ids if (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 1) else \
-            torch.from_numpy(host).to(device)
+    table, n = _planes.device_ids(ids, device, 'boundary_counts', 'ids', validate=validate, allow_empty=False,
+                                  trusted_must_be_contiguous=False)
     if (gt_binary or pred_binary) and n != 1:
         raise DevaHipError(f'boundary_counts: binary planes hold one object (got {n} ids)')
     if radius is None:
@@ -191,16 +158,15 @@ def boundary_counts(gt: torch.Tensor, pred: torch.Tensor, ids, *, bound_th: floa
     radius = int(radius)
     if not 0 <= radius <= MAX_RADIUS:
         raise DevaHipError(f'boundary_counts: radius 0 to {MAX_RADIUS} (got {radius})')
-    if out is not None and (out.dtype != torch.uint32 or tuple(out.shape) != (n, FIELDS)):
-        raise DevaHipError(f'boundary_counts: `out` must be uint32 [{n},{FIELDS}]')
+    _planes.check_out(out, (n, FIELDS), 'boundary_counts')
     need = boundary_scratch_bytes(h, w)
     if scratch is not None and (scratch.dtype != torch.uint8 or scratch.dim() != 1 or scratch.numel() < need):
         raise DevaHipError(f'boundary_counts: `scratch` must be uint8 [{need}] or longer')
-    gt, pred, table = _on_device(gt, 'gt'), _on_device(pred, 'pred'), _on_device(table, 'ids', 4)
+    gt, pred = _planes.on_device(gt, 'gt', 'boundary_counts'), _planes.on_device(pred, 'pred', 'boundary_counts')
+    table = _planes.on_device(table, 'ids', 'boundary_counts', 4)
     if fast:
-        pred_lut = _on_device(pred_lut, 'pred_lut', 2)
-    if out is not None and not (out.is_cuda and out.is_contiguous()):
-        raise DevaHipError('boundary_counts: `out` must be a contiguous tensor on the HIP device')
+        pred_lut = _planes.on_device(pred_lut, 'pred_lut', 'boundary_counts', 2)
+    _planes.check_out_on_device(out, 'boundary_counts')
     if scratch is not None and not (scratch.is_cuda and scratch.is_contiguous() and scratch.data_ptr() % 16 == 0):
         raise DevaHipError('boundary_counts: `scratch` must be a contiguous 16-byte aligned tensor on the HIP device')
     if scratch is None:

@@ -258,6 +258,18 @@ def _upload(a: np.ndarray, device: torch.device) -> torch.Tensor:
     return t.pin_memory().to(device, non_blocking=True)
 
 
+def _pinned_copy(counts: torch.Tensor):
+    """-> (host, event): a device tensor on its way into pinned memory and the event that says it has arrived (a host
+    tensor is there already: itself and None)"""
+    if not counts.is_cuda:
+        return counts, None
+    host = torch.empty(counts.shape, dtype=counts.dtype, pin_memory=True)
+    host.copy_(counts, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+    return host, event
+
+
 def _as_plane(x, device: torch.device, gt: bool) -> torch.Tensor:
     if isinstance(x, np.ndarray):
         if x.ndim == 2 and x.dtype != np.int32 and (gt or x.dtype != np.int64):
@@ -415,14 +427,7 @@ class VideoPanopticScorer:
                                              validate=False)
         else:
             counts = metrics.panoptic_counts(gt, _upload(gt_table, device), pred, _upload(pred_table, device), validate=False)
-        event = None
-        if counts.is_cuda:
-            host = torch.empty(counts.shape, dtype=counts.dtype, pin_memory=True)
-            host.copy_(counts, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record()
-        else:
-            host = counts
+        host, event = _pinned_copy(counts)
         self._frames.append(_Frame(host, event, [VOID, OTHER] + gt_table.tolist(), [VOID, OTHER] + pred_table.tolist(),
                                    [dict(s) for s in gt_segments_info], [dict(s) for s in pred_segments_info], pred, channel_ids))
 

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from deva.hip import vos_metrics
+from deva.inference.panoptic_quality import _pinned_copy, _upload
 
 GLOBAL_HEADER = ['J&F-Mean', 'J-Mean', 'J-Recall', 'J-Decay', 'F-Mean', 'F-Recall', 'F-Decay']
 SEQUENCE_HEADER = ['Sequence', 'J-Mean', 'F-Mean']
@@ -58,14 +59,6 @@ def sequence_statistics(values) -> Tuple[float, float, float]:
 
 
 # ------------------------------------------------------------------------------------------ the scorer
-def _upload(a: np.ndarray, device: torch.device) -> torch.Tensor:
-    """a host array to the device without waiting for the stream: through pinned memory"""
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    if device.type != 'cuda':
-        return t
-    return t.pin_memory().to(device, non_blocking=True)
-
-
 def _as_plane(x, device: torch.device, gt: bool) -> torch.Tensor:
     allowed = (np.uint8, np.int32) if gt else (np.uint8, np.int32, np.int64)
     if isinstance(x, np.ndarray):
@@ -142,15 +135,7 @@ class VideoObjectScorer:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=device)
         counts = vos_metrics.boundary_counts(gt, pred, self._ids_dev, bound_th=self.bound_th, pred_lut=lut, binary=bool(binary),
                                              scratch=self._scratch if device.type == 'cuda' else None, validate=False)
-        event = None
-        if counts.is_cuda:
-            host = torch.empty(counts.shape, dtype=counts.dtype, pin_memory=True)
-            host.copy_(counts, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record()
-        else:
-            host = counts
-        self._frames.append(_Frame(host, event))
+        self._frames.append(_Frame(*_pinned_copy(counts)))
 
     # ---------------------------------------------------------------- host arithmetic
     def end_video(self) -> None:
