@@ -31,7 +31,7 @@ def tapped(key_long, shr_long, n_long, key_work, shr_work, n_work, qk, qe, k, us
     res = real(key_long, shr_long, n_long, key_work, shr_work, n_work, qk, qe, k, usage_fix, splits)
     n, hw = n_long + n_work, qk.shape[1]
     if L.deva_affinity_prefilter_enabled(n, hw, k):
-        ws = ops._AFF_WS[(qk.device, torch.cuda.current_stream(qk.device).cuda_stream)]
+        ws = ops._AFF_WS[ops._stream_key(qk.device)]
         L.deva_affinity_read_stats(ws.data_ptr(), n, hw, k, out, torch.cuda.current_stream().cuda_stream)
         print(f'  read N={n} HW={hw}: flag {out[0]} largest sub-list {out[1]} (cap 32) largest query {out[2]} mean '
               f'candidates/query {out[3] / 1000:.1f} ranges {out[4]}')

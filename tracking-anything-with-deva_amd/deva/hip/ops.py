@@ -14,7 +14,7 @@ import torch
 from . import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SQUARE_PLUS_ONE, CONV_FAMILIES, ENSEMBLE_MAX_VARIANTS, KLAYOUT_CHUNK32,
                KLAYOUT_Q4, KLAYOUT_TAP_MAJOR, ConvDesc, ConvPlan, DevaHipError, EnsembleVariant, check, lib)
 
-__all__ = ['PackedConv', 'pack_conv', 'conv2d', 'conv_plan', 'ConvLaunchInfo', 'ConvPlanInfo', 'split_fallbacks', 'PackedStem', 'pack_stem', 'stem7x7', 'pad2d', 'usage_init', 'gather_s2', 'maxpool3x3s2', 'upsample2x_add', 'upsample2x_add_ds2', 'clip_index', 'upsample2x_add_map', 'upsample2x_add_ds2_map', 'area_downsample',
+__all__ = ['PackedConv', 'pack_conv', 'conv2d', 'conv_plan', 'ConvLaunchInfo', 'ConvPlanInfo', 'split_fallbacks', 'release_stream_scratch', 'PackedStem', 'pack_stem', 'stem7x7', 'pad2d', 'usage_init', 'gather_s2', 'maxpool3x3s2', 'upsample2x_add', 'upsample2x_add_ds2', 'clip_index', 'upsample2x_add_map', 'upsample2x_add_ds2_map', 'area_downsample',
            'aggregate', 'softmax_channels', 'upsample4x_softmax', 'cbam', 'gru_update',
            'affinity_topk', 'BankPrep', 'affinity_dense', 'dense_read', 'affinity_candidates', 'affinity_merge', 'usage_update', 'readout_sparse', 'bank_append', 'bank_gather_rows',
            'bank_export', 'rank', 'rank_select', 'evict_select', 'similarity_dense', 'softmax_columns',
@@ -242,10 +242,15 @@ def _make_room(cache: dict) -> None:
         cache.pop(next(iter(cache)))
 
 
+def _stream_key(device) -> Tuple[int, int]:
+    """key of the per-(device, stream) caches: the device INDEX (`cuda` and `cuda:0` are one device, one entry) and the
+    raw handle of torch's current stream on it"""
+    return (_dev_index(device), _stream(device))
+
 
 def _workspace(device) -> torch.Tensor:
     """split-K scratch, one per (device, stream): launches on different streams never share partial sums"""
-    key = (device, _stream(device))
+    key = _stream_key(device)
     ws = _WORKSPACE.get(key)
     if ws is None:
         _make_room(_WORKSPACE)
@@ -260,7 +265,7 @@ _SPLIT_RING = 4096  # flag slots per (device, stream); re-zeroed (one fill launc
 
 def _dev_index(device) -> int:
     """torch.device('cuda') and torch.device('cuda:0') name the same device when 0 is current"""
-    d = torch.device(device)
+    d = device if isinstance(device, torch.device) else torch.device(device)
     if d.type != 'cuda':
         return -1
     return torch.cuda.current_device() if d.index is None else d.index
@@ -273,15 +278,27 @@ def _evict_split_rings() -> None:
         (dev, _), (ring, _) = next(iter(_SPLIT_FLAGS.items()))
         if ring.is_cuda:
             torch.cuda.synchronize(ring.device)
-        _SPLIT_EVICTED[_dev_index(dev)] = _SPLIT_EVICTED.get(_dev_index(dev), 0) + int(ring.sum().item())
+        _SPLIT_EVICTED[dev] = _SPLIT_EVICTED.get(dev, 0) + int(ring.sum().item())
         _SPLIT_FLAGS.pop(next(iter(_SPLIT_FLAGS)))
+
+
+def release_stream_scratch(device) -> None:
+    """drop the scratch this module keeps for the current stream of `device` (split-K workspace, hand-over and dense-read
+    buffers, the split-flag ring with its count folded into the device's total): for a transient side stream that is done.
+    Synchronises that stream only; the next call on the stream allocates afresh."""
+    key = _stream_key(device)
+    for cache in (_WORKSPACE, _AFF_WS, _DENSE_WS):
+        cache.pop(key, None)
+    ent = _SPLIT_FLAGS.pop(key, None)
+    if ent is not None:
+        _SPLIT_EVICTED[key[0]] = _SPLIT_EVICTED.get(key[0], 0) + int(ent[0].sum().item())  # (.item(): waits for the stream)
 
 
 def _split_flag(device) -> int:
     """device address of a zeroed int the next split convolution may raise (deva_conv_desc.split_flag): slots of a
     per-(device, stream) ring; when the ring wraps, the raised slots are added to the ring's running total (slot
     _SPLIT_RING, read by `split_fallbacks`) and the ring is cleared -- two launches per _SPLIT_RING convolutions"""
-    key = (device, _stream(device))
+    key = _stream_key(device)
     ent = _SPLIT_FLAGS.get(key)
     if ent is None:
         _evict_split_rings()
@@ -303,7 +320,7 @@ def split_fallbacks(device) -> int:
         torch.cuda.synchronize(torch.device('cuda', want))  # rings of OTHER streams (key-encoder prefetch) are read below
     total = _SPLIT_EVICTED.get(want, 0)
     for (dev, _), (ring, _) in _SPLIT_FLAGS.items():
-        if _dev_index(dev) == want:
+        if dev == want:
             total += int(ring.sum().item())
     return total
 
@@ -711,7 +728,7 @@ def _affinity_workspace(elems: int, device) -> torch.Tensor:
     """hand-over buffer between the two affinity kernels, kept alive (grow-only) per device and stream:
     deva_affinity_topk rewrites every list length and the live part of every list before
     deva_affinity_finalize reads them"""
-    key = (device, _stream(device))
+    key = _stream_key(device)
     ws = _AFF_WS.get(key)
     if ws is None:
         _make_room(_AFF_WS)
@@ -828,11 +845,13 @@ def dense_read(key_long, shr_long, n_long: int, key_work, shr_work, n_work: int,
     L = lib()
     n = n_long + n_work
     need = int(L.deva_dense_read_scratch(n, hw))
-    key = (qk.device, _stream(qk.device))
+    key = _stream_key(qk.device)
     ws = _DENSE_WS.get(key)
     if ws is None or ws.numel() * 8 < need:
-        # bounded by the library (~256 MiB at most); grown exactly, dropped first if the allocator runs short
-        _DENSE_WS.pop(key, None)
+        # bounded by the library (~256 MiB at most); grown exactly, dropped first if the allocator runs short; at most
+        # _MAX_STREAM_CACHES streams keep one, like the other per-stream caches
+        if _DENSE_WS.pop(key, None) is None:
+            _make_room(_DENSE_WS)
         ws = _DENSE_WS[key] = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=qk.device)
     probs = None
     if return_probs:
@@ -853,9 +872,9 @@ def affinity_last_read_flag(device) -> int:
     """test hook: fall-back flag of the last pre-filtered read on the current stream of `device` (synchronises);
     0 = the fp16 pre-filter produced the result, otherwise the fp32 kernels took over (bit 0: non-finite bank,
     1: negative / non-finite query, 2: a candidate sub-list overflowed, 3: too many candidates to re-score)"""
-    ws = _AFF_WS.get((device, _stream(device)))
+    ws = _AFF_WS.get(_stream_key(device))
     if ws is None:
-        raise DevaHipError('affinity_last_read_flag: no read has run on this stream')
+        raise DevaHipError('affinity_last_read_flag: no read has run on this stream (or its buffer was evicted)')
     return int(lib().deva_affinity_read_flag(_p(ws, torch.int64), _stream()))
 
 
