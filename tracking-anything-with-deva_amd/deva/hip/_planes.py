@@ -1,5 +1,5 @@
-"""Argument handling that the two scorers (`deva.hip.metrics`, `deva.hip.vos_metrics`) share.  `fn` is the wrapper's
-name as it stands in front of every message ('panoptic_counts', 'boundary_counts')."""
+"""Argument handling that the scorers (`deva.hip.metrics`, `deva.hip.vos_metrics`, `deva.hip.pair_metrics`) share.  `fn` is the wrapper's
+name as it stands in front of every message ('panoptic_counts', 'boundary_counts', 'pair_counts')."""
 import numpy as np
 import torch
 

@@ -12,6 +12,8 @@ toolkits' published behaviour, neither toolkit is part of this repository):
   sequence_statistics  mean, recall and decay of one object's values over its frames
   VideoObjectScorer    fed frame by frame, e.g. from `FrameResultSaver(frame_hook=...)`
   score_directory      the same scorer fed from two PNG trees: a finished run against its annotations
+
+The unsupervised protocol's assignment of the tracker's own ids to objects is `unsup_quality.py`, built on this module.
 """
 import os
 import warnings
