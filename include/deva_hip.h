@@ -475,7 +475,10 @@ int deva_usage_update(uint64_t* usage_fix, int64_t offset, float* use, float* li
  * [tok_lo, tok_hi) contribute (pass 0, INT_MAX for the whole bank): a bank shard adds its own terms
  * and the partial read-outs are summed over the shards.
  * map_long / map_work (NULL = identity): value-sharded storage -- the value arenas hold only the rows this rank
- * owns; map[token within the segment] = local row, < 0 = the row lives on another rank (its owner adds that term). */
+ * owns; map[token within the segment] = local row, < 0 = the row lives on another rank (its owner adds that term).
+ * A term that does not contribute (token outside [tok_lo, tok_hi), map entry < 0) is SKIPPED, not added with weight 0:
+ * its stand-in row (row 0 of the segment's arena, which may be uninitialised on a rank without local rows) is never read
+ * into the sum, so a NaN there cannot reach out. */
 int deva_readout_sparse(const int32_t* idx, const float* weight, int hw, int k,
                         const float* val_long, int n_long, const float* val_work, int cv,
                         float* out, int tok_lo, int tok_hi, const int32_t* map_long,

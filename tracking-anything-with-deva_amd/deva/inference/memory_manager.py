@@ -549,6 +549,23 @@ class MemoryManager:
         self.long_mem.add(proto_key, proto_val, proto_shr, selection=None, supposed_bucket_id=bucket_id,
                           token_major=True)
 
+    @staticmethod
+    def partial_prototype_values(aff: torch.Tensor, P: int, owned_rows: torch.Tensor,
+                                 values: List[torch.Tensor]) -> List[torch.Tensor]:
+        """value-sharded storage, ONE rank's share of the prototype values, no collective: aff [n_cand, ld] is the
+        potentiation matrix (ld = P rounded up to 32), owned_rows the int64 offsets among the n_cand candidates of the
+        rows this rank holds, values one token-major [n_own, CV] tensor per object (those rows, in order).  -> one
+        [P, CV] tensor per object, aff[owned_rows, :P]^T @ value: a GEMM with K = n_own through deva_conv2d; exact zeros
+        for a rank that owns no candidate.  The sum over the ranks is the unsharded prototype value."""
+        n_own = int(owned_rows.numel())
+        gemm_own = ops.PackedConv(aff.index_select(0, owned_rows).contiguous(), None, n_own, P, aff.shape[1], 1, 1) if n_own else None
+        parts = []
+        for v in values:
+            cv = v.shape[1]
+            parts.append(ops.conv2d(gemm_own, v.contiguous().reshape(1, n_own, 1, cv)).view(P, cv) if n_own
+                         else torch.zeros((P, cv), dtype=torch.float32, device=aff.device))
+        return parts
+
     def consolidation(self, candidate_key: torch.Tensor, candidate_shrinkage: torch.Tensor,
                       candidate_selection: torch.Tensor, candidate_value: Dict[int, torch.Tensor],
                       usage: Tuple[torch.Tensor, torch.Tensor], *, owned_rows: Optional[torch.Tensor] = None):
@@ -571,18 +588,11 @@ class MemoryManager:
         proto_val = {}
         if owned_rows is not None:
             import torch.distributed as dist
-            n_own = int(owned_rows.numel())
-            gemm_own = ops.PackedConv(aff.index_select(0, owned_rows).contiguous(), None, n_own, P, aff.shape[1], 1, 1) if n_own else None
             # the partial sums of ALL objects travel in one collective (one all_reduce per object is latency-bound with
             # many objects; the sum per element is the same)
             objs = list(candidate_value)
             world = dist.get_world_size(self._shard_group)
-            parts = []
-            for obj in objs:
-                v = candidate_value[obj]
-                cv = v.shape[1]
-                parts.append(ops.conv2d(gemm_own, v.contiguous().reshape(1, n_own, 1, cv)).view(P, cv) if n_own
-                             else torch.zeros((P, cv), dtype=torch.float32, device=aff.device))
+            parts = self.partial_prototype_values(aff, P, owned_rows, [candidate_value[obj] for obj in objs])
             if parts:
                 stacked = torch.stack(parts, 0)
                 dist.all_reduce(stacked, op=dist.ReduceOp.SUM, group=self._shard_group)
