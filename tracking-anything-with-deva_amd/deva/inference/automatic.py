@@ -127,13 +127,14 @@ class AutomaticProcessor(FrameLoop):
     (the loop is `FrameLoop`'s; a detection is incorporated with `incremental=True`).
 
     Every key of `CONFIG_KEYS` must be in `core.config`.  `capacity` is the `ProposalFilter`'s (masks that may pass the
-    drops in one frame)."""
+    drops in one frame), and so is `min_mask_region_area` (0: off; above 0 the holes and islands below that area go from
+    every kept mask before the masks are assembled)."""
     config_keys = CONFIG_KEYS
     incorporate_keywords = {'incremental': True}
 
-    def __init__(self, core, segmenter, *, capacity: int = 512, saver=None):
+    def __init__(self, core, segmenter, *, capacity: int = 512, saver=None, min_mask_region_area: int = 0):
         super().__init__(core, saver)
-        self.segmenter, self.capacity = segmenter, int(capacity)
+        self.segmenter, self.capacity, self.min_mask_region_area = segmenter, int(capacity), int(min_mask_region_area)
         self._filter = None
 
     # ------------------------------------------------------------------ auto_segment
@@ -142,7 +143,8 @@ class AutomaticProcessor(FrameLoop):
         if flt is None or (flt.height, flt.width) != (h, w):   # once per processor, again when the frame size changes
             flt = self._filter = ProposalFilter(h, w, capacity=self.capacity,
                                                 pred_iou_thresh=self.core.config['SAM_PRED_IOU_THRESHOLD'],
-                                                mask_threshold=getattr(self.segmenter, 'mask_threshold', 0.0))
+                                                mask_threshold=getattr(self.segmenter, 'mask_threshold', 0.0),
+                                                min_mask_region_area=self.min_mask_region_area)
         return flt
 
     def segment(self, image_np: np.ndarray, forward_mask: Optional[torch.Tensor],
