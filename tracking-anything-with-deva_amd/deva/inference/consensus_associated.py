@@ -13,8 +13,17 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from deva.hip import ops
+from deva.hip import ops, rle
 from deva.utils.tensor_utils import pad_divide_by, unpad
+
+
+def rle_masks(rles, size: Optional[Tuple[int, int]] = None, *, device=None) -> torch.Tensor:
+    """the proposals of one frame as the reference's referring readers hand them over (video_reader.py:178-184: every
+    `segmentation_from_dict` decoded and put through the reader's nearest `mask_transform`): COCO run lengths in any form
+    `deva.hip.rle.parse_counts` takes -> float32 [N,OH,OW] of 0.0 / 1.0 on the device at `size` (the masks' own when None),
+    ready to be a frame's `masks` entry of `find_consensus_with_established_association`.  Decode and resize are one
+    kernel; no pycocotools, no host plane."""
+    return rle.decode(rles, size, dtype=torch.float32, device=device)
 
 
 def spatial_alignment(src_ti: int, src_image: torch.Tensor, src_mask: torch.Tensor, tar_ti: int,

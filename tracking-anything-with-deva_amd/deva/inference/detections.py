@@ -27,13 +27,17 @@ it on the device (`ops.prompt_points`: three launches and one copy of 8 bytes pe
 The text-prompted path (grounding_dino.py:101-142) is `text_detections`: the detector's fp32 boxes through
 `ops.box_nms_xyxy`, the kept ones to a box-prompted segmenter batch by batch, the best candidate mask per box chosen and
 binarised on the device by `ops.box_mask_select`, then `assemble_with_text`: two small host copies per detection frame.
-`deva.inference.with_text.TextPromptedProcessor` is its frame loop."""
+`deva.inference.with_text.TextPromptedProcessor` is its frame loop.
+
+Detections that arrive as COCO run lengths (a detector's "COCO results" file: `CocoResults`) go through `rle_detections`:
+`deva.hip.rle.decode` puts the byte planes on the device at the assembly size and the two functions above take them from
+there."""
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from deva.hip import ops
+from deva.hip import ops, rle
 from deva.inference.object_info import ObjectInfo
 from deva.utils.tensor_utils import pad_divide_by, unpad
 
@@ -243,3 +247,73 @@ def text_detections(boxes, confidences, class_ids, segmenter, frame_hw: Tuple[in
         logits, scores = segmenter.predict_boxes(boxes_px[first:first + per_batch])
         ops.box_mask_select(logits, scores, threshold, out=planes[first:first + logits.shape[0]])
     return assemble_with_text(planes, [conf_host[k] for k in keep], [classes[k] for k in keep], size)
+
+
+# ------------------------------------------------------------------------------------------ detections from run lengths
+_RLE_POLICIES = ('text', 'large', 'small')
+
+
+def rle_detections(annotations: Sequence[dict], size: Optional[Tuple[int, int]] = None, *, policy: str = 'text',
+                   score_threshold: Optional[float] = None, overlap_threshold: float = 0.8, consistent_ids: bool = False,
+                   source_size: Optional[Tuple[int, int]] = None, device=None) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+    """one frame of a detector's "COCO results" (`[{'segmentation': {'size', 'counts'}, 'score', 'category_id'?}, ...]`,
+    the masks as COCO run lengths in any form `deva.hip.rle.parse_counts` takes) -> what `incorporate_detection` takes:
+    (int64 [OH,OW] index mask on the device, [ObjectInfo]).
+
+    The masks are decoded on the device (`deva.hip.rle.decode`) straight at `size` (the masks' own when None; otherwise
+    the nearest resize of a frame reader's mask transform, fused into the decode), and the byte planes go as they are
+    into `assemble_with_text` (`policy='text'`: painter's order, `category_id` carried, None where absent) or
+    `assemble_automatic` ('large': `suppress_small_objects=True` with `overlap_threshold`; 'small': False, see
+    `consistent_ids` there).  `score_threshold`: annotations whose score is below it are left out before anything is
+    decoded.  No annotation (left) gives an empty mask of `size`, which must then be given."""
+    if policy not in _RLE_POLICIES:
+        raise ValueError(f'rle_detections: policy must be one of {_RLE_POLICIES} (got {policy!r})')
+    kept = [a for a in annotations if score_threshold is None or float(a['score']) >= score_threshold]
+    if not kept:
+        if size is None:
+            raise ValueError('rle_detections: no annotation is left and no `size` says how large the empty mask is')
+        return torch.zeros((int(size[0]), int(size[1])), dtype=torch.int64, device=torch.device('cuda' if device is None else device)), []
+    planes = rle.decode([a['segmentation'] for a in kept], size, dtype=torch.uint8, source_size=source_size, device=device)
+    scores = [float(a['score']) for a in kept]
+    if policy == 'text':
+        return assemble_with_text(planes, scores, [a.get('category_id') for a in kept])
+    return assemble_automatic(planes, scores, suppress_small_objects=policy == 'large', overlap_threshold=overlap_threshold,
+                              consistent_ids=consistent_ids)
+
+
+class CocoResults:
+    """a "COCO results" file (Mask2Former, SAM exporters, any COCO evaluator's input): a list of
+    {'image_id', 'category_id', 'score', 'segmentation': {'size', 'counts'}}, grouped by `image_id` in the order of first
+    appearance, the annotations of an image in file order.  Host bookkeeping only: nothing is decoded until a frame is
+    asked for."""
+
+    def __init__(self, path_or_list):
+        if isinstance(path_or_list, (str, bytes)) or hasattr(path_or_list, '__fspath__'):
+            import json
+            with open(path_or_list) as f:
+                path_or_list = json.load(f)
+        self.frames = {}
+        for k, ann in enumerate(path_or_list):
+            if not isinstance(ann, dict) or 'image_id' not in ann or 'segmentation' not in ann or 'score' not in ann:
+                raise ValueError(f"CocoResults: entry {k} must hold 'image_id', 'score' and 'segmentation'")
+            self.frames.setdefault(ann['image_id'], []).append(ann)
+
+    def __len__(self) -> int:
+        return len(self.frames)
+
+    def __contains__(self, image_id) -> bool:
+        return image_id in self.frames
+
+    def __iter__(self):
+        return iter(self.frames.items())
+
+    def image_ids(self) -> list:
+        return list(self.frames)
+
+    def annotations(self, image_id) -> List[dict]:
+        """the annotations of one image; an image the file does not mention has none"""
+        return self.frames.get(image_id, [])
+
+    def detections(self, image_id, size: Optional[Tuple[int, int]] = None, **kw) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+        """`rle_detections` of one image"""
+        return rle_detections(self.annotations(image_id), size, **kw)

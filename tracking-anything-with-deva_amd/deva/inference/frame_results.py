@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from deva.hip import ops
+from deva.hip import ops, rle
 
 # ------------------------------------------------------------------------------------------ colours
 def long_id_colors(ids: Sequence[int]) -> np.ndarray:
@@ -200,6 +200,28 @@ def launch_frame(object_manager, prob: torch.Tensor, size=None, *, image=None, r
     pending = PendingFrame((oh, ow), products, segments, tmp_ids, host_stats, n, host_bounds, host_planes, event)
     pending.channel_ids = ids
     return pending
+
+
+# ------------------------------------------------------------------------------------------ reading a video_json back
+def read_video_json(video_json, size: Optional[Tuple[int, int]] = None, *, dtype=torch.uint8, device=None):
+    """the `video_json` that `FrameResultSaver(dataset='burst')` builds (the dict, or the path of a JSON file that holds
+    it) -> per frame (file_name, ids, scores, planes): the segments' ids and scores as lists in file order and their masks
+    as planes [n,H,W] on the device (`deva.hip.rle.decode`: uint8 0 / 1, or float32), `planes[k]` being `labels == ids[k]`
+    of the frame as it was saved.  `size` resizes on the way (nearest, fused into the decode).  A frame without segments
+    gives planes of [0,H,W] at the size of the last frame that had any (or `size`; [0,0,0] before either is known)."""
+    if not isinstance(video_json, dict):
+        import json
+        with open(video_json) as f:
+            video_json = json.load(f)
+    known = None if size is None else (int(size[0]), int(size[1]))
+    for frame in video_json['segmentations']:
+        segments = frame['segmentations']
+        if segments:
+            planes = rle.decode([s['rle'] for s in segments], size, dtype=dtype, device=device)
+            known = tuple(planes.shape[-2:])
+        else:
+            planes = torch.zeros((0,) + (known or (0, 0)), dtype=dtype, device=torch.device('cuda' if device is None else device))
+        yield frame['file_name'], [s['id'] for s in segments], [s['score'] for s in segments], planes
 
 
 # ------------------------------------------------------------------------------------------ saver
