@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import DevaHipError, _native, _planes
+from .mask_runs import encode, encode_labels  # noqa: F401  (the other direction: planes -> run lengths, libdeva_mask_runs.so)
 from .ops import _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

@@ -31,7 +31,7 @@ from deva.inference.object_info import ObjectInfo
 from deva.inference.proposals import ProposalFilter
 from deva.utils.tensor_utils import frame_to_network_input
 
-__all__ = ['AutomaticProcessor', 'BufferedFrame', 'FrameLoop', 'CONFIG_KEYS']
+__all__ = ['AutomaticProcessor', 'BufferedFrame', 'FrameLoop', 'RecordedProcessor', 'CONFIG_KEYS']
 
 CONFIG_KEYS = ('size', 'suppress_small_objects', 'temporal_setting', 'num_voting_frames', 'detection_every',
                'SAM_NUM_POINTS_PER_SIDE', 'SAM_NUM_POINTS_PER_BATCH', 'SAM_PRED_IOU_THRESHOLD', 'SAM_OVERLAP_THRESHOLD')
@@ -58,12 +58,16 @@ class FrameLoop:
     The configuration is `core.config`; every key of `config_keys` must be there (a missing one raises KeyError with its
     name: no default is invented).
     `saver`: anything with `save_mask(prob, frame_name, need_resize=, shape=, image_np=)`, e.g. `FrameResultSaver`.
+    `recorder`: a `detections.DetectionRecorder`; every result of `_detect` is recorded under the frame's name before it
+    is used (in the semi-online setting that is each buffered frame's detection, not the vote).  Without one the loop is
+    call for call the same.
     `next_voting_frame` starts at num_voting_frames - 1, as the demos set it."""
     config_keys: Tuple[str, ...] = ()
     incorporate_keywords: Dict = {}
 
-    def __init__(self, core, saver=None):
-        self.core, self.saver = core, saver
+    def __init__(self, core, saver=None, recorder=None):
+        self.core, self.saver, self.recorder = core, saver, recorder
+        self.frame_name = None          # of the frame `_detect` is asked about
         for key in self.config_keys:
             if key not in core.config:
                 raise KeyError(key)
@@ -73,6 +77,13 @@ class FrameLoop:
 
     def _detect(self, image: torch.Tensor, image_np: np.ndarray) -> Tuple[torch.Tensor, List[ObjectInfo]]:
         raise NotImplementedError
+
+    def _detection(self, image: torch.Tensor, image_np: np.ndarray, frame_name: str) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+        self.frame_name = frame_name
+        mask, segments_info = self._detect(image, image_np)
+        if self.recorder is not None:
+            self.recorder.add(frame_name, mask, segments_info)
+        return mask, segments_info
 
     def _emit(self, produced: List, prob: torch.Tensor, frame_name: str, image_np: np.ndarray) -> None:
         produced.append((frame_name, prob))
@@ -89,7 +100,7 @@ class FrameLoop:
         produced: List[Tuple[str, torch.Tensor]] = []
         if cfg['temporal_setting'] == 'semionline':
             if ti + cfg['num_voting_frames'] > self.next_voting_frame:
-                mask, segments_info = self._detect(image, image_np)
+                mask, segments_info = self._detection(image, image_np, frame_name)
                 info = {'frame': [frame_name], 'shape': [h, w]}
                 core.add_to_temporary_buffer(BufferedFrame(image, mask, segments_info, ti, info, image_np))   # wait for more
                 if ti == self.next_voting_frame:
@@ -105,7 +116,7 @@ class FrameLoop:
                 self._emit(produced, core.step(image, None, None), frame_name, image_np)    # standard propagation
         elif cfg['temporal_setting'] == 'online':
             if ti % cfg['detection_every'] == 0:
-                mask, segments_info = self._detect(image, image_np)
+                mask, segments_info = self._detection(image, image_np, frame_name)
                 prob = core.incorporate_detection(image, mask, segments_info, **self.incorporate_keywords)
             else:
                 prob = core.step(image, None, None)
@@ -132,8 +143,8 @@ class AutomaticProcessor(FrameLoop):
     config_keys = CONFIG_KEYS
     incorporate_keywords = {'incremental': True}
 
-    def __init__(self, core, segmenter, *, capacity: int = 512, saver=None, min_mask_region_area: int = 0):
-        super().__init__(core, saver)
+    def __init__(self, core, segmenter, *, capacity: int = 512, saver=None, min_mask_region_area: int = 0, recorder=None):
+        super().__init__(core, saver, recorder)
         self.segmenter, self.capacity, self.min_mask_region_area = segmenter, int(capacity), int(min_mask_region_area)
         self._filter = None
 
@@ -184,3 +195,24 @@ class AutomaticProcessor(FrameLoop):
     def _detect(self, image: torch.Tensor, image_np: np.ndarray) -> Tuple[torch.Tensor, List[ObjectInfo]]:
         forward_mask = detections.estimate_forward_mask(self.core, image) if self.core.memory.engaged else None
         return self.segment(image_np, forward_mask, device=image.device)
+
+
+class RecordedProcessor(FrameLoop):
+    """the frame loop over detections that were computed once and saved (the reference's evaluation/eval_with_detections.py),
+    here over a recording of this package's own processors: `results` is a `detections.CocoResults` of a file that a
+    `DetectionRecorder` wrote, and a detection is `results.detections(frame name, detection_size, policy='recorded')`:
+    exactly the pair the recorded run's `_detect` returned.  A frame the file does not mention is an empty detection.
+
+    No configuration keys of its own (the loop's: size, temporal_setting, num_voting_frames, detection_every).
+    `incorporate_keywords`: those of the processor that was recorded ({'incremental': True} for `AutomaticProcessor`, none
+    for `TextPromptedProcessor`)."""
+
+    def __init__(self, core, results, *, saver=None, incorporate_keywords: Optional[Dict] = None):
+        super().__init__(core, saver)
+        self.results = results
+        self.incorporate_keywords = dict(incorporate_keywords or {})
+
+    def _detect(self, image: torch.Tensor, image_np: np.ndarray) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+        h, w = image_np.shape[:2]
+        size = detections.detection_size(h, w, self.core.config['size'])
+        return self.results.detections(self.frame_name, size, policy='recorded', device=image.device)

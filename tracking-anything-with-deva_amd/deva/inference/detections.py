@@ -31,7 +31,10 @@ binarised on the device by `ops.box_mask_select`, then `assemble_with_text`: two
 
 Detections that arrive as COCO run lengths (a detector's "COCO results" file: `CocoResults`) go through `rle_detections`:
 `deva.hip.rle.decode` puts the byte planes on the device at the assembly size and the two functions above take them from
-there."""
+there.  The other direction is `DetectionRecorder`: what a processor's `_detect` returned, frame by frame, written as such a
+file with the run lengths encoded on the device (`deva.hip.rle.encode_labels`, `encode`), so that
+`rle_detections(..., policy='recorded')` gives the recorded pair back and `deva.inference.automatic.RecordedProcessor`
+re-runs the tracker over the same detections without the segmenter."""
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -250,7 +253,20 @@ def text_detections(boxes, confidences, class_ids, segmenter, frame_hw: Tuple[in
 
 
 # ------------------------------------------------------------------------------------------ detections from run lengths
-_RLE_POLICIES = ('text', 'large', 'small')
+_RLE_POLICIES = ('text', 'large', 'small', 'recorded')
+
+
+def _recorded(annotations: Sequence[dict], size, source_size, device) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+    """what `DetectionRecorder.add` wrote for one frame -> the pair it was given: the pixels of plane k get `id_k`, in file
+    order, and every entry is listed, whether a pixel holds its id or not"""
+    for k, a in enumerate(annotations):
+        if 'id' not in a:
+            raise ValueError(f"rle_detections: entry {k} carries no 'id': policy='recorded' reads what DetectionRecorder wrote")
+    planes = rle.decode([a['segmentation'] for a in annotations], size, dtype=torch.uint8, source_size=source_size, device=device)
+    mask = torch.zeros(planes.shape[1:], dtype=torch.int64, device=planes.device)
+    for plane, a in zip(planes, annotations):
+        mask = torch.where(plane != 0, int(a['id']), mask)
+    return mask, [ObjectInfo(int(a['id']), a.get('category_id'), score=a['score']) for a in annotations]
 
 
 def rle_detections(annotations: Sequence[dict], size: Optional[Tuple[int, int]] = None, *, policy: str = 'text',
@@ -264,8 +280,11 @@ def rle_detections(annotations: Sequence[dict], size: Optional[Tuple[int, int]] 
     the nearest resize of a frame reader's mask transform, fused into the decode), and the byte planes go as they are
     into `assemble_with_text` (`policy='text'`: painter's order, `category_id` carried, None where absent) or
     `assemble_automatic` ('large': `suppress_small_objects=True` with `overlap_threshold`; 'small': False, see
-    `consistent_ids` there).  `score_threshold`: annotations whose score is below it are left out before anything is
-    decoded.  No annotation (left) gives an empty mask of `size`, which must then be given."""
+    `consistent_ids` there).  `policy='recorded'`: the annotations are a `DetectionRecorder`'s, every one with its 'id', and
+    the result is the recorded pair itself, nothing is assembled again: uncompacted ids and a listed id that no pixel
+    holds (its run lengths are [H * W]) come back as they were.  `score_threshold`: annotations whose score is below it
+    are left out before anything is decoded.  No annotation (left) gives an empty mask of `size`, which must then be
+    given."""
     if policy not in _RLE_POLICIES:
         raise ValueError(f'rle_detections: policy must be one of {_RLE_POLICIES} (got {policy!r})')
     kept = [a for a in annotations if score_threshold is None or float(a['score']) >= score_threshold]
@@ -273,12 +292,62 @@ def rle_detections(annotations: Sequence[dict], size: Optional[Tuple[int, int]] 
         if size is None:
             raise ValueError('rle_detections: no annotation is left and no `size` says how large the empty mask is')
         return torch.zeros((int(size[0]), int(size[1])), dtype=torch.int64, device=torch.device('cuda' if device is None else device)), []
+    if policy == 'recorded':
+        return _recorded(kept, size, source_size, device)
     planes = rle.decode([a['segmentation'] for a in kept], size, dtype=torch.uint8, source_size=source_size, device=device)
     scores = [float(a['score']) for a in kept]
     if policy == 'text':
         return assemble_with_text(planes, scores, [a.get('category_id') for a in kept])
     return assemble_automatic(planes, scores, suppress_small_objects=policy == 'large', overlap_threshold=overlap_threshold,
                               consistent_ids=consistent_ids)
+
+
+class DetectionRecorder:
+    """detections as they are made, kept as the entries of a "COCO results" file that `CocoResults` reads: per object
+    {'image_id', 'id', 'score', 'segmentation': {'size', 'counts'}} and 'category_id' when the object has one.  The run
+    lengths are encoded on the device; the host receives the run boundaries, never a plane."""
+
+    def __init__(self, path=None):
+        self.path = path
+        self.annotations: List[dict] = []
+
+    def add(self, image_id, mask: torch.Tensor, segments_info: Sequence[ObjectInfo]) -> None:
+        """the (index mask, [ObjectInfo]) pair that `incorporate_detection` takes, under `image_id` (a frame's name); an
+        object that no pixel holds is listed with the run lengths [H * W]"""
+        segments_info = list(segments_info)
+        if not segments_info:
+            return
+        for obj, seg in zip(segments_info, rle.encode_labels(mask, [obj.id for obj in segments_info])):
+            score, category = obj.scores[0], obj.category_ids[0]
+            entry = {'image_id': image_id, 'id': int(obj.id), 'score': None if score is None else float(score), 'segmentation': seg}
+            if category is not None:
+                entry['category_id'] = int(category)
+            self.annotations.append(entry)
+
+    def add_planes(self, image_id, planes: torch.Tensor, scores: Sequence, category_ids: Optional[Sequence] = None,
+                   threshold: Optional[float] = None) -> None:
+        """raw proposals: [N,H,W] planes on the device (uint8 / bool, or float32 logits with `threshold`; they may
+        overlap) with a score each, numbered 1.. in the call's order"""
+        scores = scores.tolist() if hasattr(scores, 'tolist') else list(scores)
+        categories = None if category_ids is None else (category_ids.tolist() if hasattr(category_ids, 'tolist') else list(category_ids))
+        if len(scores) != planes.shape[0] or (categories is not None and len(categories) != planes.shape[0]):
+            raise ValueError(f'add_planes: {planes.shape[0]} planes, {len(scores)} scores'
+                             + ('' if categories is None else f' and {len(categories)} category ids'))
+        for k, seg in enumerate(rle.encode(planes, threshold=threshold)):
+            entry = {'image_id': image_id, 'id': k + 1, 'score': float(scores[k]), 'segmentation': seg}
+            if categories is not None and categories[k] is not None:
+                entry['category_id'] = int(categories[k])
+            self.annotations.append(entry)
+
+    def write(self, path=None) -> str:
+        """the entries as a JSON list -> the path written"""
+        import json
+        path = self.path if path is None else path
+        if path is None:
+            raise ValueError('DetectionRecorder.write: no path was given')
+        with open(path, 'w') as f:
+            json.dump(self.annotations, f)
+        return path
 
 
 class CocoResults:

@@ -52,8 +52,8 @@ class TextPromptedProcessor(FrameLoop):
     config_keys = CONFIG_KEYS
     incorporate_keywords = {}
 
-    def __init__(self, core, detector, segmenter, *, saver=None, boxes_per_batch: int = 16, capacity: int = 256):
-        super().__init__(core, saver)
+    def __init__(self, core, detector, segmenter, *, saver=None, boxes_per_batch: int = 16, capacity: int = 256, recorder=None):
+        super().__init__(core, saver, recorder)
         self.detector, self.segmenter = detector, segmenter
         self.boxes_per_batch, self.capacity = int(boxes_per_batch), int(capacity)
 
