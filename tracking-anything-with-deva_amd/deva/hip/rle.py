@@ -19,6 +19,7 @@ import torch
 
 from . import DevaHipError, _native, _planes
 from .mask_runs import encode, encode_labels  # noqa: F401  (the other direction: planes -> run lengths, libdeva_mask_runs.so)
+from .rle_overlap import intersections, iou  # noqa: F401  (mask overlaps from the run lengths, libdeva_rle_overlap.so)
 from .ops import _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
