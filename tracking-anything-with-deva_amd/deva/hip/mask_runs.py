@@ -6,7 +6,8 @@ and without `pycocotools` (rules E1-E7 of the header).  The inverse of `deva.hip
 The device gives the run boundaries of all masks back to back (`count`, then `write`: the contract of `ops.mask_rle`);
 the host turns them into counts and compressed strings with the arithmetic `FrameResultSaver` already uses
 (`frame_results.rle_counts`, `coco_strings`).  `encode_labels` does the same for an index mask and a list of ids on the
-existing `ops.mask_rle`.
+existing `ops.mask_rle`.  With `text='device'` (an opt-in of both) the strings are coded on the device as well
+(`deva.hip.rle_text`, libdeva_rle_text.so) and only their bytes come to the host; the results are the same.
 
 A seventh library next to libdeva_hip.so, the three scorers, the regions and the decoder, loaded lazily by `lib()`; the
 conventions are those of `deva.hip.rle`: `check` raises `DevaHipError` with the library's text, there is no CPU path."""
@@ -18,7 +19,7 @@ from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import DevaHipError, _native, ops
+from . import DevaHipError, _native, ops, rle_text
 from .ops import _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -33,6 +34,7 @@ MASK_CHUNK = 256
 SEGMENT_BYTES = 12
 DTYPES = {torch.uint8: 0, torch.float32: 1}   # DEVA_RUNS_U8, DEVA_RUNS_F32
 FORMS = ('string', 'bytes', 'counts')
+TEXT = ('host', 'device')   # where the compressed strings are coded
 STATS = ('area', 'x_min', 'y_min', 'x_max', 'y_max')
 
 
@@ -258,9 +260,10 @@ def _to_pinned(t: torch.Tensor) -> torch.Tensor:
 class PendingRuns:
     """an encoding whose results are on their way to the host; `finish()` waits for them"""
 
-    def __init__(self, size, form, n, bounds, total, stats, capacity, event):
+    def __init__(self, size, form, n, bounds, total, stats, capacity, event, text=None):
         self.size, self.form, self.capacity = size, form, capacity
         self._n, self._bounds, self._total, self._stats, self._event = n, bounds, total, stats, event
+        self._text = text          # a `rle_text.PendingText`: the strings were coded on the device, `bounds` stayed there
         self._result = None
 
     def finish(self) -> List[dict]:
@@ -271,6 +274,9 @@ class PendingRuns:
             total = int(self._total[-1]) if self._total is not None else 0
             if total > self.capacity:
                 raise DevaHipError(f'encode: the masks have {total} run boundaries, the capacity is {self.capacity}')
+            if self._text is not None:
+                self._result = _text_records(self._text.finish(), None if self._stats is None else self._stats.numpy(), self.size, self.form)
+                return self._result
             self._result = _records(self._n.numpy(), self._bounds.numpy()[:total], None if self._stats is None else self._stats.numpy(),
                                     self.size, self.form)
         return self._result
@@ -297,9 +303,27 @@ def _records(n: np.ndarray, bounds: np.ndarray, stats: Optional[np.ndarray], siz
     return out
 
 
+def _text_records(bodies: List[bytes], stats: Optional[np.ndarray], size: Tuple[int, int], form: str) -> List[dict]:
+    """`_records` for strings that were coded on the device"""
+    h, w = size
+    out = [{'size': [h, w], 'counts': b if form == 'bytes' else b.decode('ascii')} for b in bodies]
+    if stats is not None:
+        for rec, row in zip(out, stats.tolist()):
+            rec['area'] = row[0]
+            rec['bbox'] = row[1:] if row[0] > 0 else None
+    return out
+
+
+def _text_mode(text, form: str, fn: str) -> bool:
+    """-> the strings are coded on the device ('counts' has no string: it takes the host path whatever `text` says)"""
+    if text not in TEXT:
+        raise DevaHipError(f'{fn}: text must be one of {TEXT} (got {text!r})')
+    return text == 'device' and form != 'counts'
+
+
 def encode(planes: torch.Tensor, *, threshold: Optional[float] = None, form: str = 'string', stats: bool = False,
            capacity: Optional[int] = None, max_masks: Optional[int] = None, max_scratch: Optional[int] = None,
-           before_wait: Optional[Callable[[], None]] = None):
+           before_wait: Optional[Callable[[], None]] = None, text: str = 'host'):
     """[N,H,W] planes on the device (uint8 or bool: 1 iff not 0; float32 with `threshold`: 1 iff value > threshold, E1)
     -> [{'size': [H, W], 'counts': ...}] in mask order, `counts` as `form` says: 'string' (the ASCII text `pycocotools`
     gives after `.decode('ascii')`), 'bytes', or 'counts' (a list of int).  With `stats=True` every entry also holds
@@ -309,11 +333,17 @@ def encode(planes: torch.Tensor, *, threshold: Optional[float] = None, form: str
     right before that: nothing has synchronised up to there).  With `capacity=` nothing synchronises: `bounds` holds
     `capacity` boundaries and the call returns a `PendingRuns`, whose `finish()` waits, raises if the masks had more
     boundaries than that and otherwise returns the same list.  More masks than one call of the library takes
-    (`runs_limits()`; `max_masks` / `max_scratch` lower the limits) are walked in chunks that fill one `bounds`."""
+    (`runs_limits()`; `max_masks` / `max_scratch` lower the limits) are walked in chunks that fill one `bounds`.
+
+    `text='device'` (forms 'string' and 'bytes'): the strings are coded on the device from `bounds`
+    (`rle_text.encode_text`), into a buffer sized from what the call already knows, `max_chars(H * W)` characters for each
+    of the `room + N` counts there can be; the characters and their lengths come to the host in place of the boundaries,
+    with the same one wait.  The result is identical."""
     fn = 'encode'
     planes, code, threshold_value = _prepare(planes, threshold, fn)
     if form not in FORMS:
         raise DevaHipError(f'{fn}: form must be one of {FORMS} (got {form!r})')
+    on_device = _text_mode(text, form, fn)
     if capacity is not None and int(capacity) < 0:
         raise DevaHipError(f'{fn}: capacity must not be negative (got {capacity})')
     n, h, w = planes.shape
@@ -342,25 +372,27 @@ def encode(planes: torch.Tensor, *, threshold: Optional[float] = None, form: str
     for part in counted:
         write(part, bounds, room)
     event = None
-    host = [_to_pinned(t) if t is not None else None for t in (n_dev, bounds, totals, stats_dev)]
+    coded = rle_text.encode_text(n_dev, base, bounds, (h, w), pending=True, record=False) if on_device else None
+    host = [_to_pinned(t) if t is not None else None for t in (n_dev, None if on_device else bounds, totals, stats_dev)]
     if device.type == 'cuda':
         event = torch.cuda.Event()
         event.record(torch.cuda.current_stream(device))
-    pending = PendingRuns((h, w), form, host[0], host[1], host[2], host[3], room, event)
+    pending = PendingRuns((h, w), form, host[0], host[1], host[2], host[3], room, event, coded)
     return pending.finish() if capacity is None else pending
 
 
 # ------------------------------------------------------------------------------------------ labels
-def encode_labels(labels: torch.Tensor, ids: Sequence[int], *, form: str = 'string') -> List[dict]:
+def encode_labels(labels: torch.Tensor, ids: Sequence[int], *, form: str = 'string', text: str = 'host') -> List[dict]:
     """an int64, int32 or int16 [H,W] label plane on the device (a detection's index mask) and a list of ids -> the run
     lengths of `labels == id` per id, in the order of `ids`: [{'size': [H, W], 'counts': ...}].  An id that no pixel
     holds gives [H * W].  The ids are mapped to channels with torch ops and the planes' objects are disjoint, so this is
-    the existing `ops.mask_rle`: no new kernel."""
+    the existing `ops.mask_rle`: no new kernel.  `text='device'`: the strings are coded on the device (`encode`)."""
     fn = 'encode_labels'
     if not isinstance(labels, torch.Tensor) or labels.dim() != 2 or labels.dtype not in (torch.int64, torch.int32, torch.int16):
         raise DevaHipError(f'{fn}: labels must be an int64, int32 or int16 [H,W] tensor on the device')
     if form not in FORMS:
         raise DevaHipError(f'{fn}: form must be one of {FORMS} (got {form!r})')
+    on_device = _text_mode(text, form, fn)
     ids = [int(i) for i in ids]
     if len(set(ids)) != len(ids):
         raise DevaHipError(f'{fn}: the ids must be distinct (got {ids})')
@@ -376,4 +408,8 @@ def encode_labels(labels: torch.Tensor, ids: Sequence[int], *, form: str = 'stri
     at = torch.searchsorted(table, wide).clamp_(max=len(ids) - 1)  # the one id a pixel can equal
     channel = torch.where(table[at] == wide, channel_of[at], torch.zeros((), dtype=torch.int16, device=labels.device))
     n, bounds = ops.mask_rle(channel.contiguous(), len(ids) + 1)
+    if on_device:                                        # (`n` is on the host; the background has no boundaries in `bounds`)
+        per = n[1:].to(torch.int32).contiguous()
+        base = torch.cumsum(per, 0, dtype=torch.int64) - per
+        return _text_records(rle_text.encode_text(per.to(bounds.device), base.to(bounds.device), bounds, (h, w)), None, (h, w), form)
     return _records(n[1:].cpu().numpy(), bounds.cpu().numpy(), None, (h, w), form)

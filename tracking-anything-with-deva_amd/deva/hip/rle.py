@@ -5,7 +5,9 @@ the frame reader's nearest resize fused in (rules D1-D6 of the header).
 
 The host parses the text (`parse_counts`: the inverse of `frame_results.coco_strings`, vectorised over all characters
 of all masks of a call), checks the counts (D2), turns them into run starts by one cumulative sum and sends ONE int32
-array per call to the device; the kernel does the rest.  `pycocotools` is not needed.
+array per call to the device; the kernel does the rest.  `pycocotools` is not needed.  With `parse='device'` (an opt-in
+of `decode`, `records`, `intersections` and `iou`) the texts go up as they are and libdeva_rle_text.so builds the run
+array there (`deva.hip.rle_text`); the results are the same.
 
 A sixth library next to libdeva_hip.so, the three scorers and the regions, loaded lazily by `lib()`; the conventions are
 those of `deva.hip.regions`: `check` raises `DevaHipError` with the library's text, there is no CPU path."""
@@ -17,7 +19,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import DevaHipError, _native, _planes
+from . import DevaHipError, _native, _planes, rle_text
 from .mask_runs import encode, encode_labels  # noqa: F401  (the other direction: planes -> run lengths, libdeva_mask_runs.so)
 from .rle_overlap import intersections, iou  # noqa: F401  (mask overlaps from the run lengths, libdeva_rle_overlap.so)
 from .ops import _stream
@@ -31,6 +33,7 @@ MAX_MASKS = 65536
 MAX_WORDS = 1 << 26
 DTYPES = {torch.uint8: 0, torch.float32: 1}   # DEVA_RLE_U8, DEVA_RLE_F32
 MAX_CHARS = 12                                 # characters of one coded value: 60 bits
+PARSE = ('host', 'device')                     # where the text of a mask is parsed
 
 
 class Limits(Structure):
@@ -240,17 +243,114 @@ def parse_counts(obj) -> np.ndarray:
 
 # ------------------------------------------------------------------------------------------ D2 and the run array
 class Parsed(NamedTuple):
-    counts: np.ndarray      # int64, all masks back to back
+    counts: Optional[np.ndarray]   # int64, all masks back to back (None after a parse on the device: `counts_of` has them)
     per_mask: np.ndarray    # int64 [N]: runs of every mask
     height: int
     width: int
+    device: Optional[list] = None  # after a parse on the device: its [rle_text.RunChunk], the run arrays there and here
 
 
-def parse_checked(rles: Sequence, source_size: Optional[Tuple[int, int]] = None, fn: str = 'decode') -> Parsed:
+def _parse_mode(parse, fn: str) -> bool:
+    if parse not in PARSE:
+        raise DevaHipError(f'{fn}: parse must be one of {PARSE} (got {parse!r})')
+    return parse == 'device'
+
+
+def _texts_and_size(rles: Sequence, source_size) -> Optional[Tuple[List[bytes], Tuple[int, int]]]:
+    """every mask's text as bytes and the one size of the call, when every mask is a text (a dict's `counts` included) and
+    the sizes raise no question; None otherwise: the host path then parses, or says what is wrong"""
+    bodies, size = [], None if source_size is None else (int(source_size[0]), int(source_size[1]))
+    try:
+        for obj in rles:
+            if isinstance(obj, dict):
+                if 'counts' not in obj or 'size' not in obj or len(obj['size']) != 2:
+                    return None
+                s = (int(obj['size'][0]), int(obj['size'][1]))
+                if size is not None and s != size:
+                    return None
+                size, obj = s, obj['counts']
+            if not _is_text(obj):
+                return None
+            bodies.append(obj.encode('latin-1') if isinstance(obj, str) else bytes(obj))
+    except (TypeError, ValueError, UnicodeEncodeError):
+        return None
+    if size is None or not bodies or size[0] < 1 or size[1] < 1 or size[0] * size[1] >= 2**31:
+        return None
+    return bodies, size
+
+
+class _DeviceParse:
+    """a parse that libdeva_rle_text.so has been handed (`_begin_device_parse`): `finish()` -> Parsed.  Several of them
+    (the two sides of an overlap) share their second wait: `flags_checked()` on each in turn, `fetch()` on each, one wait,
+    `parsed()` on each."""
+
+    def __init__(self, pending, size, verdict):
+        self.pending, self.size, self.verdict = pending, size, verdict
+
+    def flags_checked(self) -> None:
+        flags = self.pending.flags()
+        if flags:
+            self.verdict(flags)
+
+    def parsed(self) -> 'Parsed':
+        chunks = self.pending.complete()
+        per_mask = np.concatenate([np.diff(c.host[:c.hi - c.lo + 1].astype(np.int64)) - 1 for c in chunks])
+        return Parsed(None, per_mask, self.size[0], self.size[1], chunks)
+
+    def finish(self) -> 'Parsed':
+        self.pending.finish(self.verdict)
+        return self.parsed()
+
+
+def _begin_device_parse(rles: Sequence, source_size, fn: str, device, max_masks, max_words, spare: int) -> Optional[_DeviceParse]:
+    """`parse_checked` with the run arrays built by libdeva_rle_text.so, launched and not waited for; None when the call
+    takes the host path (a mask that is no text, a size that is missing or differs, a text above one call's limits, no
+    mask at all)"""
+    found = _texts_and_size(rles, source_size)
+    if found is None:
+        return None
+    bodies, size = found
+    top = rle_text.text_limits()
+    parts = rle_text.text_chunks([len(b) for b in bodies], min(top.max_masks, max_masks or top.max_masks),
+                                 min(top.max_words, max_words or top.max_words))
+    if parts is None:
+        return None
+
+    def host_verdict(flags):
+        parse_checked(rles, source_size, fn)             # raises the message that names the mask
+        raise DevaHipError(f'{fn}: the device parser flags the texts ({flags:#x}: ' +
+                           '; '.join(t for b, t in rle_text.FLAGS.items() if flags & b) + ') and the host parser accepts them')
+    return _DeviceParse(rle_text.PendingParse(bodies, size, 'cuda' if device is None else device, parts, spare), size, host_verdict)
+
+
+def counts_of(parsed: Parsed) -> np.ndarray:
+    """the counts of all masks back to back, int64: `parsed.counts`, or after a parse on the device the differences of
+    the starts of its run arrays"""
+    if parsed.counts is not None:
+        return parsed.counts
+    pieces = []
+    for c in parsed.device:
+        n = c.hi - c.lo
+        first, starts = c.host[:n + 1].astype(np.int64), c.host[n + 1:].astype(np.int64)
+        pieces.append(np.delete(np.diff(starts), first[1:n] - 1))        # (without the differences across two masks)
+    return np.concatenate(pieces) if pieces else np.zeros(0, dtype=np.int64)
+
+
+def parse_checked(rles: Sequence, source_size: Optional[Tuple[int, int]] = None, fn: str = 'decode', *, parse: str = 'host', device=None,
+                  max_masks: Optional[int] = None, max_words: Optional[int] = None, spare: int = 0) -> Parsed:
     """parse and hold to D2: one size (the dicts', else `source_size`), 1 <= H * W < 2^31, no negative count, every mask's
-    counts sum to H * W.  An error names the mask."""
+    counts sum to H * W.  An error names the mask.
+
+    `parse='device'`: when every mask is a `str` / `bytes` (a dict's `counts` included) the joined bytes go up once and
+    `deva.hip.rle_text` builds the run arrays on `device`, in chunks within `max_masks` / `max_words`; they come back in
+    `Parsed.device` after two waits.  What the device flags is parsed again here, so the error is the host path's.  A
+    call with any other mask takes the host path whole."""
     if isinstance(rles, (dict, str, bytes)) or not hasattr(rles, '__len__'):
         raise DevaHipError(f'{fn}: a list of masks expected (got {type(rles).__name__})')
+    if _parse_mode(parse, fn):
+        begun = _begin_device_parse(rles, source_size, fn, device, max_masks, max_words, spare)
+        if begun is not None:
+            return begun.finish()
     counts, per_mask, sizes = parse_many(rles)
     size = None if source_size is None else (int(source_size[0]), int(source_size[1]))
     for k, s in enumerate(sizes):
@@ -285,7 +385,7 @@ def run_array(parsed: Parsed, lo: int, hi: int) -> np.ndarray:
     per = parsed.per_mask[lo:hi]
     n = hi - lo
     begin = int(parsed.per_mask[:lo].sum())
-    counts = parsed.counts[begin:begin + int(per.sum())]
+    counts = counts_of(parsed)[begin:begin + int(per.sum())]
     first = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(per + 1, out=first[1:])
     mask_of = np.repeat(np.arange(n), per)
@@ -335,7 +435,7 @@ def _check_out(out, n: int, oh: int, ow: int, dtype, fn: str) -> None:
 
 def decode(rles: Sequence, size: Optional[Tuple[int, int]] = None, *, dtype=torch.uint8, out: Optional[torch.Tensor] = None,
            source_size: Optional[Tuple[int, int]] = None, device=None, max_masks: Optional[int] = None,
-           max_words: Optional[int] = None) -> torch.Tensor:
+           max_words: Optional[int] = None, parse: str = 'host') -> torch.Tensor:
     """N run-length masks (each in any form `parse_counts` takes) -> planes [N, OH, OW] on the device, uint8 0 / 1 or
     float32 0.0 / 1.0 (D4).  `size`: the output size; the masks' own (one per call, D2) when None; otherwise the nearest
     resize of `F.interpolate(mode='nearest')` is fused in (D3) and no source-size plane exists.  `source_size`: for masks
@@ -344,14 +444,26 @@ def decode(rles: Sequence, size: Optional[Tuple[int, int]] = None, *, dtype=torc
     Everything is parsed and checked (D2) before anything is launched; an error names the mask and leaves `out` as it
     was.  Per call of the library one int32 array (pinned) goes up on the current stream, and one launch follows on it;
     nothing synchronises.  More masks or runs than one call takes (`rle_limits()`; `max_masks` / `max_words` lower the
-    limits) are walked in chunks."""
+    limits) are walked in chunks.
+
+    `parse='device'`: the texts are parsed on the device (`parse_checked`): per chunk the joined bytes go up instead, the
+    run array is built there and its host copy, which the library checks as ever, comes back in two waits."""
     fn = 'decode'
     code = _dtype_code(dtype, fn)
-    parsed = parse_checked(rles, source_size, fn)
+    target = out.device if isinstance(out, torch.Tensor) else torch.device('cuda' if device is None else device)
+    if _parse_mode(parse, fn) and target.type == 'cuda':
+        limits = _limits(max_masks, max_words, fn)
+        with torch.cuda.device(target):
+            parsed = parse_checked(rles, source_size, fn, parse=parse, device=target, max_masks=limits[0], max_words=limits[1])
+    else:
+        parsed = parse_checked(rles, source_size, fn)
     oh, ow = _sizes(parsed, size, fn)
     n = int(parsed.per_mask.size)
     _check_out(out, n, oh, ow, dtype, fn)
-    parts = chunks(parsed.per_mask, *_limits(max_masks, max_words, fn), fn)
+    if parsed.device is None:
+        parts = chunks(parsed.per_mask, *_limits(max_masks, max_words, fn), fn)
+    else:
+        parts = [(c.lo, c.hi) for c in parsed.device]
     if out is None:
         device = torch.device('cuda' if device is None else device)
         if device.type != 'cuda':
@@ -360,17 +472,20 @@ def decode(rles: Sequence, size: Optional[Tuple[int, int]] = None, *, dtype=torc
     elif not out.is_cuda:
         raise DevaHipError(f'{fn}: `out` must live on the HIP device (got {out.device}); there is no CPU path')
     _planes.check_out_on_device(out, fn)
-    arrays = [run_array(parsed, lo, hi) for lo, hi in parts]
+    arrays = [run_array(parsed, lo, hi) for lo, hi in parts] if parsed.device is None else [c.host for c in parsed.device]
     for (lo, hi), words in zip(parts, arrays):           # the library's own D2 on every chunk, before the first launch of the call
         check(lib().deva_rle_check(words.ctypes.data, words.size, hi - lo, parsed.height, parsed.width), 'deva_rle_check')
     with torch.cuda.device(out.device):
         stream = _stream(out.device)
-        for (lo, hi), words in zip(parts, arrays):
-            host = torch.empty(words.size, dtype=torch.int32, pin_memory=True)
-            host.numpy()[:] = words
-            runs = host.to(out.device, non_blocking=True)
+        for c, ((lo, hi), words) in enumerate(zip(parts, arrays)):
+            if parsed.device is None:
+                host = torch.empty(words.size, dtype=torch.int32, pin_memory=True)
+                host.numpy()[:] = words
+                host_ptr, runs = host.data_ptr(), host.to(out.device, non_blocking=True)
+            else:                                        # the run array is in place on the device; `words` is its host copy
+                host_ptr, runs = words.ctypes.data, parsed.device[c].device
             part = out[lo:hi]
-            check(lib().deva_rle_decode(host.data_ptr(), runs.data_ptr(), words.size, hi - lo, parsed.height, parsed.width, oh, ow, code,
+            check(lib().deva_rle_decode(host_ptr, runs.data_ptr(), words.size, hi - lo, parsed.height, parsed.width, oh, ow, code,
                                         part.data_ptr(), stream), 'deva_rle_decode')
     return out
 
@@ -382,11 +497,12 @@ class Records(NamedTuple):
     bbox: np.ndarray    # int64 [N,4]: x0, y0, x1, y1 inclusive at source size; -1 four times for an empty mask
 
 
-def records(rles: Sequence, source_size: Optional[Tuple[int, int]] = None) -> Records:
-    """D5, on the host from the counts alone (`pycocotools`' area / toBbox in the convention of `FrameResult.segments`)"""
-    parsed = parse_checked(rles, source_size, 'records')
+def records(rles: Sequence, source_size: Optional[Tuple[int, int]] = None, *, parse: str = 'host', device=None) -> Records:
+    """D5, on the host from the counts alone (`pycocotools`' area / toBbox in the convention of `FrameResult.segments`).
+    `parse='device'`: the texts are parsed on `device` (`parse_checked`) and the counts come from its run arrays."""
+    parsed = parse_checked(rles, source_size, 'records', parse=parse, device=device)
     h, n = parsed.height, int(parsed.per_mask.size)
-    per, counts = parsed.per_mask, parsed.counts
+    per, counts = parsed.per_mask, counts_of(parsed)
     mask_of = np.repeat(np.arange(n), per)
     local = np.arange(counts.size) - np.repeat(np.cumsum(per) - per, per)
     ends = _segment_cumsum(counts, mask_of)

@@ -2,7 +2,9 @@
 one list of COCO run-length masks with every mask of another, taken from the run lengths on the device (rules O1-O9 of the
 header), and `pycocotools.mask.iou` on top of it.  No plane is decoded: per side the host parses the text
 (`rle.parse_checked`), builds the run array of `deva_rle.h` (`rle.run_array`) and from it the boxes (`boxes_and_areas`)
-and sends them up in ONE int32 array; two launches follow.  `pycocotools` is not needed.
+and sends them up in ONE int32 array; two launches follow.  `pycocotools` is not needed.  With `parse='device'` the
+texts go up instead and libdeva_rle_text.so builds the run arrays there (`rle.parse_checked`); the host copy that comes
+back is checked as ever and gives the boxes, which follow the run array on the device.
 
 The public names are re-exported by `deva.hip.rle` as `rle.intersections` and `rle.iou`.
 
@@ -131,7 +133,7 @@ def pair_chunks(per_d: np.ndarray, per_g: np.ndarray, max_masks: int, max_words:
     return [(pd, pg) for pd in parts_d for pg in parts_g]
 
 
-def _parse_sides(dt: Sequence, gt: Sequence, source_size, fn: str):
+def _parse_sides(dt: Sequence, gt: Sequence, source_size, fn: str, parse: str = 'host', device=None, limits=(None, None)):
     """both sides parsed and held to O2, on one common size"""
     rle = _rle()
     sides = []
@@ -150,7 +152,33 @@ def _parse_sides(dt: Sequence, gt: Sequence, source_size, fn: str):
                 break
     if size is None and not len(sides[0]) and not len(sides[1]):
         size = (1, 1)                                  # nothing on either side: no size is needed
-    return (rle.parse_checked(sides[0], size, f'{fn}: dt'), rle.parse_checked(sides[1], size, f'{fn}: gt'))
+    if (not len(sides[0]) or not len(sides[1])) and parse in rle.PARSE:
+        parse = 'host'                                   # (O7 reads the counts of the side that is not empty)
+    names = (f'{fn}: dt', f'{fn}: gt')
+    if not rle._parse_mode(parse, fn):
+        return (rle.parse_checked(sides[0], size, names[0]), rle.parse_checked(sides[1], size, names[1]))
+    # both sides are handed to the device before either is waited for; a side that cannot go there is parsed here
+    for side in sides:
+        if isinstance(side, (dict, str, bytes)) or not hasattr(side, '__len__'):
+            return (rle.parse_checked(sides[0], size, names[0]), rle.parse_checked(sides[1], size, names[1]))   # (raises)
+    begun = [rle._begin_device_parse(side, size, name, device, limits[0], limits[1], 4) for side, name in zip(sides, names)]
+    parsed = [None, None]
+    for k, b in enumerate(begun):                        # dt's errors before gt's, as on the host path
+        if b is None:
+            parsed[k] = rle.parse_checked(sides[k], size, names[k])
+        else:
+            b.flags_checked()
+    waiting = [b for b in begun if b is not None]
+    for b in waiting:
+        b.pending.fetch()
+    if waiting:
+        event = rle.rle_text._event(waiting[0].pending.device)
+        if event is not None:
+            event.synchronize()
+    for k, b in enumerate(begun):
+        if b is not None:
+            parsed[k] = b.parsed()
+    return tuple(parsed)
 
 
 class _Side(NamedTuple):
@@ -194,12 +222,21 @@ def boxes_and_areas(words: np.ndarray, n: int, height: int) -> Tuple[np.ndarray,
 
 
 def _side(parsed, lo: int, hi: int, side: int, pin: bool) -> _Side:
-    words = _rle().run_array(parsed, lo, hi)
+    """after a parse on the device the run array is in place there, with room for the boxes behind it: `device` is set and
+    only the boxes are still to go up"""
+    chunk = None if parsed.device is None else next(c for c in parsed.device if (c.lo, c.hi) == (lo, hi))
+    words = _rle().run_array(parsed, lo, hi) if chunk is None else chunk.host
     check(lib().deva_overlap_check(words.ctypes.data, words.size, hi - lo, parsed.height, parsed.width, side), 'deva_overlap_check')
     host = torch.empty(words.size + 4 * (hi - lo), dtype=torch.int32, pin_memory=pin)
     host.numpy()[:words.size] = words
     host.numpy()[words.size:] = boxes_and_areas(words, hi - lo, parsed.height)[0].reshape(-1)
-    return _Side(host, None, int(words.size), hi - lo)
+    return _Side(host, None if chunk is None else chunk.device[:host.numel()], int(words.size), hi - lo)
+
+
+def _parts(parsed, max_masks: int, max_words: int, name: str) -> List[Tuple[int, int]]:
+    if parsed.device is not None:
+        return [(c.lo, c.hi) for c in parsed.device]
+    return _rle().chunks(np.asarray(parsed.per_mask), max_masks, max_words, name)
 
 
 def _launch(dt: _Side, gt: _Side, height: int, width: int, scratch, inter, area_d, area_g, stream) -> None:
@@ -250,7 +287,8 @@ def _to_pinned(t: torch.Tensor) -> torch.Tensor:
 
 
 def intersections(dt: Sequence, gt: Sequence, *, stream=None, source_size: Optional[Tuple[int, int]] = None, device=None,
-                  out: Optional[dict] = None, pending: bool = False, max_masks: Optional[int] = None, max_words: Optional[int] = None):
+                  out: Optional[dict] = None, pending: bool = False, max_masks: Optional[int] = None, max_words: Optional[int] = None,
+                  parse: str = 'host'):
     """D detections and G ground-truth masks (two lists; each mask in any form `rle.parse_counts` takes, all of one
     size) -> (inter [D,G], area_d [D], area_g [G]) on the device: the pixels every pair shares and every mask's area,
     exact integers (int32 tensors; the library writes uint32 below 2^31, O3).
@@ -264,17 +302,33 @@ def intersections(dt: Sequence, gt: Sequence, *, stream=None, source_size: Optio
     masks or runs on a side than one call takes (`overlap_limits()`; `max_masks` / `max_words` lower the limits) are
     walked D-chunk by G-chunk, each chunk of a side uploaded once.
 
-    With D == 0 or G == 0 nothing is launched (O7): the areas of the other side are then the host's sums of its counts."""
+    With D == 0 or G == 0 nothing is launched (O7): the areas of the other side are then the host's sums of its counts.
+
+    `parse='device'`: a side whose masks are all texts is parsed on the device, on the same stream (`rle.parse_checked`);
+    both sides are handed over before either is waited for, then one wait for their flags and one for the host copies of
+    their run arrays; the tables are the same."""
     fn = 'intersections'
     rle = _rle()
-    parsed_d, parsed_g = _parse_sides(dt, gt, source_size, fn)
+    if stream is not None and not isinstance(stream, torch.cuda.Stream):
+        raise DevaHipError(f'{fn}: `stream` must be a torch.cuda.Stream (got {type(stream).__name__})')
+    if parse == 'device':
+        limits = _limits(max_masks, max_words, fn)
+        given = [t for t in (out or {}).values() if isinstance(t, torch.Tensor)]
+        target = torch.device(device if device is not None else (given[0].device if given else (stream.device if stream is not None else 'cuda')))
+        with contextlib.ExitStack() as stack:
+            if target.type == 'cuda':
+                stack.enter_context(torch.cuda.device(target))
+                if stream is not None:
+                    stack.enter_context(torch.cuda.stream(stream))
+            parsed_d, parsed_g = _parse_sides(dt, gt, source_size, fn, parse, target, limits)
+    else:
+        parsed_d, parsed_g = _parse_sides(dt, gt, source_size, fn, parse)
     if (parsed_d.height, parsed_d.width) != (parsed_g.height, parsed_g.width):
         raise DevaHipError(f'{fn}: dt is {parsed_d.height} x {parsed_d.width}, gt is {parsed_g.height} x {parsed_g.width} (one size per call)')
     h, w = parsed_d.height, parsed_d.width
     n_d, n_g = int(parsed_d.per_mask.size), int(parsed_g.per_mask.size)
-    blocks = pair_chunks(parsed_d.per_mask, parsed_g.per_mask, *_limits(max_masks, max_words, fn), fn)
-    if stream is not None and not isinstance(stream, torch.cuda.Stream):
-        raise DevaHipError(f'{fn}: `stream` must be a torch.cuda.Stream (got {type(stream).__name__})')
+    top = _limits(max_masks, max_words, fn)
+    blocks = [(pd, pg) for pd in _parts(parsed_d, *top, f'{fn}: dt') for pg in _parts(parsed_g, *top, f'{fn}: gt')]
     given = [t for t in (out or {}).values() if isinstance(t, torch.Tensor)]
     device = torch.device(device if device is not None else (given[0].device if given else (stream.device if stream is not None else 'cuda')))
     inter = _out(out, 'inter', (n_d, n_g), device, fn)
@@ -298,7 +352,10 @@ def intersections(dt: Sequence, gt: Sequence, *, stream=None, source_size: Optio
                                             for lo, hi in rle.chunks(parsed.per_mask, MAX_MASKS, MAX_WORDS, fn)])
                     t.copy_(torch.from_numpy(areas.astype(np.int32)), non_blocking=True)
         for key, s in list(sides.items()):
-            sides[key] = s._replace(device=s.host.to(device, non_blocking=True))
+            if s.device is None:
+                sides[key] = s._replace(device=s.host.to(device, non_blocking=True))
+            else:                                         # (parsed on the device: the boxes follow the run array there)
+                s.device[s.words:].copy_(s.host[s.words:], non_blocking=True)
         for (lo_d, hi_d), (lo_g, hi_g) in blocks:
             side_d, side_g = sides[(DT, lo_d, hi_d)], sides[(GT, lo_g, hi_g)]
             scratch = torch.empty(max(side_g.words - side_g.n - 1, 1), dtype=torch.int32, device=device)
@@ -329,10 +386,11 @@ def iou_from_counts(inter: np.ndarray, area_d: np.ndarray, area_g: np.ndarray, i
     return inter.astype(np.float64) / union.astype(np.float64)
 
 
-def iou(dt: Sequence, gt: Sequence, iscrowd=None, *, source_size: Optional[Tuple[int, int]] = None, device=None) -> np.ndarray:
+def iou(dt: Sequence, gt: Sequence, iscrowd=None, *, source_size: Optional[Tuple[int, int]] = None, device=None,
+        parse: str = 'host') -> np.ndarray:
     """`pycocotools.mask.iou(dt, gt, iscrowd)` for run-length masks -> float64 [D,G] on the host: `intersections` on the
-    device, one copy of its integers, then `iou_from_counts`"""
+    device, one copy of its integers, then `iou_from_counts`.  `parse`: as `intersections` takes it."""
     if iscrowd is not None and len(iscrowd) != len(gt):
         raise DevaHipError(f'iou: iscrowd has {len(iscrowd)} entries for {len(gt)} ground-truth masks')
-    inter, area_d, area_g = intersections(dt, gt, source_size=source_size, device=device, pending=True).finish()
+    inter, area_d, area_g = intersections(dt, gt, source_size=source_size, device=device, pending=True, parse=parse).finish()
     return iou_from_counts(inter, area_d, area_g, iscrowd)
