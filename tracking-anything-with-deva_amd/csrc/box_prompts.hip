@@ -7,6 +7,7 @@
 //   select    grid (chunk, box): every workgroup derives the box's choice from its <= 16 scores (uniform loads), then
 //             streams its chunk of the chosen plane: one 16-byte load and one 4-byte store per group of four pixels.
 //             4 bytes read and 1 written per pixel and box; the planes that are not chosen are never touched.
+#include "box_choice.h"  // box_choice
 #include "box_prompt_plan.h"
 #include "common.h"
 #include "proposal_plan.h"
@@ -22,17 +23,6 @@ struct BoxSelectArgs {
   uint8_t* out;      // plane of box 0 of this launch
   int32_t* chosen;   // its choice, or NULL
 };
-
-// numpy's argmax: the first NaN if there is one, else the first maximum (-0.0 == 0.0)
-__device__ __forceinline__ int box_choice(const float* s, int n) {
-  int best = 0;
-  float v = s[0];
-  for (int m = 1; m < n; ++m) {
-    const float c = s[m];
-    if (v == v && (c != c || c > v)) best = m, v = c;
-  }
-  return best;
-}
 
 // The chosen plane is walked in the aligned space of prop_stats_kernel (proposals.hip): element e sits at the 16-byte
 // boundary below the plane plus 4 e bytes, the plane is e in [shift, shift + hw), a group of four with e % 4 == 0 is one

@@ -14,22 +14,6 @@ int proposal_chunks(int height, int width) {
   return (int)(((int64_t)height * width + 15 + kPropChunk - 1) / kPropChunk);
 }
 
-ProposalPlan proposal_plan(int capacity) {
-  ProposalPlan p;
-  p.words = (capacity + 63) / 64;
-  ScratchLayout s;
-  p.off_stats = s.take((int64_t)kPropBatch * kPropStat * 4);
-  p.off_slots = s.take((int64_t)kPropBatch * 4);
-  p.off_count = s.take(256);
-  p.off_table = s.take((int64_t)capacity * kPropRow * 4);
-  p.off_order = s.take((int64_t)capacity * 4);
-  p.off_keep = s.take((int64_t)capacity * 4);
-  p.off_nkeep = s.take(256);
-  p.off_matrix = s.take((int64_t)capacity * p.words * 8);
-  p.bytes = s.at;
-  return p;
-}
-
 static int scratch_check(const char* what, int capacity, const void* scratch, int64_t scratch_bytes) {
   DEVA_REQUIRE(capacity >= 1, "%s: a capacity of at least one mask (got %d)", what, capacity);
   DEVA_REQUIRE(capacity <= kPropMaxMasks, "%s: at most %d masks (got %d)", what, kPropMaxMasks, capacity);

@@ -3,6 +3,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "host_args.h"
+
 namespace deva {
 
 constexpr int kPropMaxMasks = 4096;   // stored masks per frame: kDetMaxMasks, and 64 lanes x one 64-bit suppression word
@@ -27,8 +29,23 @@ struct ProposalPlan {
   int64_t bytes;
 };
 
-// the layout for 1 <= capacity <= kPropMaxMasks
-ProposalPlan proposal_plan(int capacity);
+// the layout for 1 <= capacity <= kPropMaxMasks.  Defined here with internal linkage: libdeva_lowres.so (lowres/) works on the
+// same scratch and compiles the same text, and no library exports or shares a symbol for it.
+static inline ProposalPlan proposal_plan(int capacity) {
+  ProposalPlan p;
+  p.words = (capacity + 63) / 64;
+  host_args::ScratchLayout s;
+  p.off_stats = s.take((int64_t)kPropBatch * kPropStat * 4);
+  p.off_slots = s.take((int64_t)kPropBatch * 4);
+  p.off_count = s.take(256);
+  p.off_table = s.take((int64_t)capacity * kPropRow * 4);
+  p.off_order = s.take((int64_t)capacity * 4);
+  p.off_keep = s.take((int64_t)capacity * 4);
+  p.off_nkeep = s.take(256);
+  p.off_matrix = s.take((int64_t)capacity * p.words * 8);
+  p.bytes = s.at;
+  return p;
+}
 bool proposal_capacity_ok(int capacity);
 // workgroups per plane of the chunked passes: the plane's elements plus the up to 15 that align its first group
 int proposal_chunks(int height, int width);

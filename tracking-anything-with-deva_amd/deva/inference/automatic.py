@@ -17,7 +17,13 @@ The segmenter is any object with
                                          frame's own size, iou_preds fp32 [B*M]), both on the device
     reset_image()                        optional
     mask_threshold                       optional attribute (default 0.0, SAM's)
-INTEGRATION.md wraps a `SamPredictor` this way.
+and optionally, for the route without frame-sized logits (`ProposalFilter.add_lowres`, include/deva_lowres.h),
+    predict_points_lowres(points_px)     -> (low_logits fp32 [B*M,LH,LW] contiguous: the mask decoder's own output,
+                                         iou_preds fp32 [B*M]), both on the device
+    input_size                           attribute, valid after `set_image`: (IH, IW), the frame after the segmenter's
+                                         longest-side resize
+    model_size                           optional attribute (default 1024, SAM's)
+INTEGRATION.md wraps a `SamPredictor` both ways.
 
 `FrameLoop` is the loop itself; `deva.inference.with_text.TextPromptedProcessor` runs the same loop with detections
 from a text-prompted detector."""
@@ -139,13 +145,19 @@ class AutomaticProcessor(FrameLoop):
 
     Every key of `CONFIG_KEYS` must be in `core.config`.  `capacity` is the `ProposalFilter`'s (masks that may pass the
     drops in one frame), and so is `min_mask_region_area` (0: off; above 0 the holes and islands below that area go from
-    every kept mask before the masks are assembled)."""
+    every kept mask before the masks are assembled).
+
+    `lowres`: None (the default) takes the low-resolution route when the segmenter offers it (`predict_points_lowres` and
+    `input_size`) and `predict_points` otherwise; True insists on it (a segmenter without it is refused), False never
+    takes it."""
     config_keys = CONFIG_KEYS
     incorporate_keywords = {'incremental': True}
 
-    def __init__(self, core, segmenter, *, capacity: int = 512, saver=None, min_mask_region_area: int = 0, recorder=None):
+    def __init__(self, core, segmenter, *, capacity: int = 512, saver=None, min_mask_region_area: int = 0, recorder=None,
+                 lowres: Optional[bool] = None):
         super().__init__(core, saver, recorder)
         self.segmenter, self.capacity, self.min_mask_region_area = segmenter, int(capacity), int(min_mask_region_area)
+        self.lowres = detections.lowres_route(segmenter, 'predict_points_lowres', lowres)
         self._filter = None
 
     # ------------------------------------------------------------------ auto_segment
@@ -182,8 +194,13 @@ class AutomaticProcessor(FrameLoop):
         flt.reset()
         per_batch = int(cfg['SAM_NUM_POINTS_PER_BATCH'])
         for first in range(0, points_px.shape[0], per_batch):
-            logits, iou_preds = self.segmenter.predict_points(points_px[first:first + per_batch])
-            flt.add(logits, iou_preds)
+            if self.lowres:
+                low_logits, iou_preds = self.segmenter.predict_points_lowres(points_px[first:first + per_batch])
+                flt.add_lowres(low_logits, iou_preds, self.segmenter.input_size,
+                               model_size=getattr(self.segmenter, 'model_size', 1024))
+            else:
+                logits, iou_preds = self.segmenter.predict_points(points_px[first:first + per_batch])
+                flt.add(logits, iou_preds)
         if hasattr(self.segmenter, 'reset_image'):
             self.segmenter.reset_image()
         found = flt.finish()

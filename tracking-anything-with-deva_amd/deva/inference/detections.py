@@ -40,6 +40,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from deva.hip import lowres as lowres_ops
 from deva.hip import ops, rle
 from deva.inference.object_info import ObjectInfo
 from deva.utils.tensor_utils import pad_divide_by, unpad
@@ -188,9 +189,20 @@ def _host_array(values, dtype) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(values, dtype=dtype))
 
 
+def lowres_route(segmenter, method: str, lowres: Optional[bool]) -> bool:
+    """does a processor take the route without frame-sized logits (include/deva_lowres.h)?  `lowres` None: when the
+    segmenter offers `method` (`predict_points_lowres` / `predict_boxes_lowres`; its `input_size` is read after
+    `set_image`); True: it must; False: never"""
+    offered = callable(getattr(segmenter, method, None))
+    if lowres and not offered:
+        raise ops.DevaHipError(f'lowres=True: the segmenter has no `{method}`')
+    return offered if lowres is None else bool(lowres)
+
+
 def text_detections(boxes, confidences, class_ids, segmenter, frame_hw: Tuple[int, int], size: Tuple[int, int], *,
                     nms_threshold: float, boxes_per_batch: int = 16, capacity: int = 256,
-                    arena: Optional[torch.Tensor] = None, device=None) -> Tuple[torch.Tensor, List[ObjectInfo]]:
+                    arena: Optional[torch.Tensor] = None, device=None,
+                    lowres: Optional[bool] = None) -> Tuple[torch.Tensor, List[ObjectInfo]]:
     """`segment_with_text` from the detector's answer on (grounding_dino.py:101-142): `boxes` fp32 [N,4] xyxy in pixels
     of the frame, `confidences` fp32 [N], `class_ids` [N] (numpy, as GroundingDINO's wrapper returns them, or tensors; a
     class id may be None, the unmatched phrase, and passes through) -> (int64 [OH,OW] index mask on the device,
@@ -203,7 +215,12 @@ def text_detections(boxes, confidences, class_ids, segmenter, frame_hw: Tuple[in
     contiguous uint8 [capacity,H,W]; default: allocated here for the kept boxes).  Nothing synchronises per batch.
     `assemble_with_text` then makes its one copy of the record table.  The segmenter must have seen the frame
     (`set_image`); it is not asked at all when no box is given or kept.  More kept boxes than `capacity` raise
-    DevaHipError before the segmenter is asked."""
+    DevaHipError before the segmenter is asked.
+
+    A segmenter with `predict_boxes_lowres(boxes_px) -> (low fp32 [B,M,LH,LW], scores fp32 [B,M])` and an `input_size`
+    attribute (after `set_image`; `model_size` optional, 1024) is asked for those instead, and `lowres.select_masks` writes
+    the same arena slices from them: the planes of `ops.box_mask_select` on the resized logits (include/deva_lowres.h, rule
+    L6) without resizing any.  `lowres`: None takes that route when it is offered, True insists, False never takes it."""
     h, w = int(frame_hw[0]), int(frame_hw[1])
     size = (int(size[0]), int(size[1]))
     if device is None:
@@ -246,9 +263,15 @@ def text_detections(boxes, confidences, class_ids, segmenter, frame_hw: Tuple[in
               else arena.view(capacity, h, w)[:kept])
     boxes_px = boxes_dev.index_select(0, packed[:kept].to(torch.int64))
     threshold = getattr(segmenter, 'mask_threshold', 0.0)
+    use_lowres = lowres_route(segmenter, 'predict_boxes_lowres', lowres)   # (here: the segmenter is not touched before a box is kept)
     for first in range(0, kept, per_batch):
-        logits, scores = segmenter.predict_boxes(boxes_px[first:first + per_batch])
-        ops.box_mask_select(logits, scores, threshold, out=planes[first:first + logits.shape[0]])
+        if use_lowres:
+            low, scores = segmenter.predict_boxes_lowres(boxes_px[first:first + per_batch])
+            lowres_ops.select_masks(low, scores, segmenter.input_size, (h, w), threshold=threshold,
+                                    model_size=getattr(segmenter, 'model_size', 1024), out=planes[first:first + low.shape[0]])
+        else:
+            logits, scores = segmenter.predict_boxes(boxes_px[first:first + per_batch])
+            ops.box_mask_select(logits, scores, threshold, out=planes[first:first + logits.shape[0]])
     return assemble_with_text(planes, [conf_host[k] for k in keep], [classes[k] for k in keep], size)
 
 

@@ -20,7 +20,7 @@ from typing import Optional
 
 import torch
 
-from deva.hip import DevaHipError, ops, regions
+from deva.hip import DevaHipError, lowres, ops, regions
 from deva.hip.ops import ProposalResult
 
 __all__ = ['ProposalFilter', 'ProposalResult']
@@ -34,6 +34,8 @@ class ProposalFilter:
         for points in batches:                       # the generator's loop (automatic_mask_generator.py:264-268)
             logits, iou_preds = segmenter(points)    # [B,h,w] fp32, [B] fp32, on the device
             flt.add(logits, iou_preds)               # three launches, no synchronisation
+            # or, from the mask decoder's own [B,256,256] output, without the frame-sized planes:
+            # flt.add_lowres(low_logits, iou_preds, input_size)
         found = flt.finish()                         # box NMS, ONE host copy, the kept planes in keep order
         mask, segments = assemble_automatic(found.masks, found.iou_preds, suppress_small_objects=True)
 
@@ -91,6 +93,15 @@ class ProposalFilter:
     def add(self, logits: torch.Tensor, iou_preds: torch.Tensor) -> None:
         """one batch: `logits` fp32 [B,H,W] contiguous and `iou_preds` fp32 [B], both on the device; B may be 0"""
         ops.proposal_batch(self._ready(logits.device), logits, iou_preds, **self.thresholds)
+
+    def add_lowres(self, low_logits: torch.Tensor, iou_preds: torch.Tensor, input_size, *, model_size: int = 1024) -> None:
+        """one batch straight from the segmenter's mask decoder: `low_logits` fp32 [B,LH,LW] contiguous (SAM: 256 x 256) and
+        `iou_preds` fp32 [B], both on the device; `input_size` = (IH, IW), the frame after the segmenter's longest-side
+        resize (`lowres.sam_input_size(h, w, model_size)` for SAM).  The same as `add(lowres.upsample_logits(low_logits,
+        input_size, (height, width)), iou_preds)`, bit for bit, without the frame-sized fp32 planes (include/deva_lowres.h,
+        rules L1-L5); a frame may mix both kinds of batch.  Three launches, no synchronisation; B may be 0."""
+        lowres.proposal_batch(self._ready(low_logits.device), low_logits, iou_preds, input_size, model_size=model_size,
+                              **self.thresholds)
 
     def finish(self) -> ProposalResult:
         """-> the frame's `ProposalResult` (masks uint8 [K,H,W], iou_preds and stability fp32 [K] on the device; boxes

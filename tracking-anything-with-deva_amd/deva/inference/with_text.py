@@ -26,6 +26,11 @@ and the segmenter any object with
                                          M candidate masks per box, 1 <= M <= 16
     reset_image()                        optional
     mask_threshold                       optional attribute (default 0.0, SAM's)
+and optionally, for the route without frame-sized logits (`lowres.select_masks`, include/deva_lowres.h),
+    predict_boxes_lowres(boxes_px)       -> (low fp32 [B,M,LH,LW] contiguous: the mask decoder's own output, scores fp32
+                                         [B,M]), both on the device
+    input_size                           attribute, valid after `set_image`: (IH, IW), the frame after the segmenter's
+                                         longest-side resize; `model_size` optional (default 1024, SAM's)
 INTEGRATION.md wraps `groundingdino.util.inference.Model` and a `SamPredictor` this way."""
 from typing import List, Tuple
 
@@ -48,13 +53,17 @@ class TextPromptedProcessor(FrameLoop):
 
     Every key of `CONFIG_KEYS` must be in `core.config`.  config['prompt'] is split on '.' as the reference splits it
     (with_text_processor.py:42-43: no stripping, an empty string stays a class).  `boxes_per_batch` boxes go to the
-    segmenter at a time; `capacity` is the number of boxes that may be left after NMS in one frame."""
+    segmenter at a time; `capacity` is the number of boxes that may be left after NMS in one frame.  `lowres`: None (the
+    default) takes the low-resolution route when the segmenter offers `predict_boxes_lowres`, True insists on it, False
+    never takes it."""
     config_keys = CONFIG_KEYS
     incorporate_keywords = {}
 
-    def __init__(self, core, detector, segmenter, *, saver=None, boxes_per_batch: int = 16, capacity: int = 256, recorder=None):
+    def __init__(self, core, detector, segmenter, *, saver=None, boxes_per_batch: int = 16, capacity: int = 256, recorder=None,
+                 lowres=None):
         super().__init__(core, saver, recorder)
         self.detector, self.segmenter = detector, segmenter
+        self.lowres = detections.lowres_route(segmenter, 'predict_boxes_lowres', lowres)
         self.boxes_per_batch, self.capacity = int(boxes_per_batch), int(capacity)
 
     @property
@@ -73,7 +82,8 @@ class TextPromptedProcessor(FrameLoop):
                                                                            text_threshold=threshold)
         found = detections.text_detections(boxes, confidences, class_ids, self.segmenter, (h, w), size,
                                            nms_threshold=cfg['DINO_NMS_THRESHOLD'], boxes_per_batch=self.boxes_per_batch,
-                                           capacity=self.capacity, device=torch.device('cuda') if device is None else device)
+                                           capacity=self.capacity, device=torch.device('cuda') if device is None else device,
+                                           lowres=self.lowres)
         if hasattr(self.segmenter, 'reset_image'):
             self.segmenter.reset_image()
         return found
