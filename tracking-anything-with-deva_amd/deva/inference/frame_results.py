@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from deva.hip import ops, rle
+from deva.hip import ops, png as png_coder, rle
 
 # ------------------------------------------------------------------------------------------ colours
 def long_id_colors(ids: Sequence[int]) -> np.ndarray:
@@ -123,6 +123,7 @@ class PendingFrame:
         self.size, self.products, self.segments, self.tmp_ids = size, products, segments, tmp_ids
         self.host_stats, self.n, self.host_bounds, self.host_planes, self.event = host_stats, n, host_bounds, host_planes, event
         self.channel_ids = None
+        self.png = None          # a `deva.hip.png.PendingPng` when the saver codes the PNG on the device
 
     def finish(self) -> FrameResult:
         if self.event is not None:
@@ -236,10 +237,19 @@ class FrameResultSaver:
     the PNG and the `video_json` are what the reference's merge_stuff would have written from the unmerged output,
     without reading a plane twice or re-writing a file.  `frame_hook(frame_name, result, annotation)` is called by the
     worker after a frame's files are written, with the `FrameResult` (its `index` plane and `channel_ids` included) and
-    the annotation just appended: where an online scorer is fed."""
+    the annotation just appended: where an online scorer is fed.
+
+    `png='host'` (the default) is the above.  With `png='device'` the PNG's plane (`gray` or `color`) is not copied to
+    the host: `deva.hip.png.encode` codes its zlib stream on the caller's stream (include/deva_png.h) with a capacity
+    that adapts -- 64 KB at first, then twice the largest stream seen; a longer stream is copied a second time at its
+    exact size -- and the worker wraps the copied stream into the file (chunks and CRCs on the host) and writes the bytes
+    to the same path.  The file decodes to the same pixels and palette; its bytes are not PIL's and it is two to four
+    times as large.  The `blend` JPEG stays with PIL, and `FrameResult.host` then lacks the PNG's plane."""
+
+    PNG_FIRST_CAPACITY = 65536
 
     def __init__(self, output_root: str, video_name: str, *, dataset: str, object_manager, palette=None,
-                 id_postprocessor=None, frame_hook=None):
+                 id_postprocessor=None, frame_hook=None, png: str = 'host'):
         self.output_root = output_root
         self.video_name = video_name
         self.dataset = dataset.lower()
@@ -249,6 +259,11 @@ class FrameResultSaver:
         self.frame_hook = frame_hook
         if id_postprocessor is not None and self.dataset != 'vipseg':
             raise ValueError("id_postprocessor: the stuff merging belongs to dataset 'vipseg'")
+        if png not in ('host', 'device'):
+            raise ValueError(f"png: 'host' or 'device' (got {png!r})")
+        self.png = png
+        self.png_capacity = self.PNG_FIRST_CAPACITY
+        self.png_largest = 0
         self.need_remapping = False
         self.json_style = None
         self.output_postfix = None
@@ -305,8 +320,12 @@ class FrameResultSaver:
             merge = self.id_postprocessor.assign(self.object_manager.get_current_segments_info())
         pending = launch_frame(self.object_manager, prob, shape if need_resize else None,
                                image=image_np if 'blend' in planes else None, rle=self.json_style == 'burst',
-                               color='id' if long_id else 'gray', remap=self.need_remapping, planes=planes, host=planes,
+                               color='id' if long_id else 'gray', remap=self.need_remapping, planes=planes,
+                               host=planes if self.png == 'host' else planes[1:],
                                id_map=None if merge is None else merge[0], index=self.frame_hook is not None)
+        if self.png == 'device' and save_the_mask:   # the stream is coded now, on the caller's stream; nothing is waited for
+            plane = pending.products.color if long_id else pending.products.gray
+            pending.png = png_coder.encode(plane, palette=None if long_id else self.palette, capacity=self.png_capacity)
         self.queue.put((pending, frame_name, long_id) if merge is None else (pending, frame_name, long_id, merge))
 
     def end(self) -> None:
@@ -363,8 +382,15 @@ class FrameResultSaver:
                 out_img.putpalette(self.palette)
         else:
             out_img = None
-        if out_img is not None:
-            self._save_image(out_img, path.join(self._out_dir(self.output_postfix), frame_name[:-4] + '.png'))
+        coded = pending.png
+        if coded is not None:
+            data = coded.finish()
+            self.png_largest = max(self.png_largest, coded.total)
+            self.png_capacity = 2 * self.png_largest
+            self._save_bytes(data, path.join(self._out_dir(self.output_postfix), frame_name[:-4] + '.png'))
+        if out_img is not None or coded is not None:
+            if out_img is not None:
+                self._save_image(out_img, path.join(self._out_dir(self.output_postfix), frame_name[:-4] + '.png'))
             if 'blend' in result.host:
                 self._save_image(Image.fromarray(result.host['blend']),
                                  path.join(self._out_dir(self.visualize_postfix), frame_name[:-4] + '.jpg'))
@@ -373,3 +399,7 @@ class FrameResultSaver:
 
     def _save_image(self, image, where: str) -> None:
         image.save(where)
+
+    def _save_bytes(self, data: bytes, where: str) -> None:
+        with open(where, 'wb') as f:
+            f.write(data)
