@@ -5,15 +5,14 @@ costs 10-20 % on the affinity kernels without failing a single numerical test --
 in profiles/r02e_affinity_shapes.txt (items 2 and 11) -- so the compiler's own resource report is asserted here, with
 the flags of csrc/Makefile."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
+import abi_util
+from abi_util import HIPCC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'tracking-anything-with-deva_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith('.hip'))
 # once-per-frame kernels whose per-thread tables are indexed dynamically (the antialias filter taps of the input head)
 SCRATCH_BY_DESIGN = ('input_head_kernel',)
@@ -32,30 +31,11 @@ MIN_OCCUPANCY = {
 HOME = {'affinity_topk': 'affinity.hip', 'affinity_pf_pass': 'affinity_prefilter.hip', 'conv_igemm': 'conv_igemm.hip'}
 
 
-def resource_report(src, tmp_path):
-    flags = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-I' + os.path.join(ROOT, 'include'),
-             '-Rpass-analysis=kernel-resource-usage']
-    if src.startswith('affinity'):
-        flags += ['-mllvm', '-amdgpu-mfma-vgpr-form=1']
-    out = subprocess.run([HIPCC] + flags + ['-c', os.path.join(CSRC, src), '-o', str(tmp_path / (src + '.o'))],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'remark: (?:Function Name: (\S+)|\s*([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+))', line)
-        if not m:
-            continue
-        if m.group(1):
-            cur = kernels.setdefault(m.group(1), {})
-        elif cur is not None:
-            cur[m.group(2).strip()] = int(m.group(3))
-    return kernels
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not found')
 @pytest.mark.parametrize('src', SOURCES)
-def test_no_kernel_spills_or_uses_scratch(src, tmp_path):
-    kernels = resource_report(src, tmp_path)  # (empty for host-only sources such as runtime.hip)
+def test_no_kernel_spills_or_uses_scratch(src):
+    # (empty for host-only sources such as runtime.hip)
+    kernels = abi_util.kernel_resources(os.path.join(CSRC, src), ['-mllvm', '-amdgpu-mfma-vgpr-form=1'] if src.startswith('affinity') else ())
     for name, r in kernels.items():
         if any(k in name for k in SCRATCH_BY_DESIGN):
             continue

@@ -1,4 +1,4 @@
-// Host-side argument helpers of the five libraries: pointer predicates, the scratch bump layout, and the error text and
+// Host-side argument helpers of every library: pointer predicates, the scratch bump layout, and the error text and
 // REQUIRE macro that each library instantiates for itself.  Header-only, internal linkage, no HIP: every *_plan.cpp
 // and every tests/*_sanitize_main.cpp can include it, and no library exports or shares anything from it.
 #pragma once
@@ -49,7 +49,7 @@ inline bool scratch_ok(const void* scratch, int64_t scratch_bytes, int64_t need)
     va_end(ap);                                   \
   }
 
-// DEVA_REQUIRE, DEVA_METRICS_REQUIRE, DEVA_VOS_REQUIRE, DEVA_PAIR_REQUIRE and DEVA_REGIONS_REQUIRE are this with their library's set_error
+// every library's DEVA_*_REQUIRE (DEVA_REQUIRE, DEVA_METRICS_REQUIRE, ...) is this with its own set_error
 #define HOST_ARGS_REQUIRE(set_error, cond, ...) \
   do {                                          \
     if (!(cond)) {                              \

@@ -22,6 +22,8 @@
 // Every load lies inside [N][H][W], every store inside the scratch, n_out, base, total, stats and bounds[0, capacity).
 #include <hip/hip_runtime.h>
 
+#include "../block_scan.h"
+#include "../launch_check.h"
 #include "mask_runs_plan.h"
 
 namespace deva_runs {
@@ -154,34 +156,6 @@ __global__ __launch_bounds__(kBlock) void runs_stats_init_kernel(int32_t* stats,
   }
 }
 
-// inclusive scan over the wave
-template <typename V>
-__device__ __forceinline__ V wave_inclusive(V v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const V up = __shfl_up(v, d);
-    if (lane >= d) v += up;
-  }
-  return v;
-}
-
-// -> (the sum of the lanes before this one in the workgroup, the workgroup's sum); two barriers
-template <typename V>
-__device__ __forceinline__ void block_exclusive(V v, V* wave_sums, int tid, V& before, V& all) {
-  const int lane = tid & 63, wave = tid >> 6;
-  const V inclusive = wave_inclusive(v, lane);
-  if (lane == 63) wave_sums[wave] = inclusive;
-  __syncthreads();
-  before = inclusive - v;
-  all = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    if (w < wave) before += wave_sums[w];
-    all += wave_sums[w];
-  }
-  __syncthreads();   // wave_sums is written again in the next step
-}
-
 // one workgroup per mask: popcounts -> exclusive offsets, in place; n_out[k] = their sum (below 2^31: E6)
 __global__ __launch_bounds__(kBlock) void runs_scan_kernel(int32_t* off, int segments, int32_t* n_out) {
   __shared__ int wave_sums[kWaves];
@@ -197,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void runs_scan_kernel(int32_t* off, int seg
       sum += v[e];
     }
     int before, all;
-    block_exclusive(sum, wave_sums, tid, before, all);
+    block_scan::block_exclusive<block_scan::Sum>(sum, 0, wave_sums, tid, before, all);
     before += running;
 #pragma unroll
     for (int e = 0; e < kScanItems; ++e) {
@@ -213,17 +187,8 @@ __global__ __launch_bounds__(kBlock) void runs_scan_kernel(int32_t* off, int seg
 __global__ __launch_bounds__(kBlock) void runs_base_kernel(const int32_t* n_in, int n, const int64_t* first, int64_t* base,
                                                            int64_t* total) {
   __shared__ long long wave_sums[kWaves];
-  const int tid = threadIdx.x;
-  long long running = first ? (long long)*first : 0ll;
-  for (int begin = 0; begin < n; begin += DEVA_RUNS_MASK_CHUNK) {
-    const int i = begin + tid;
-    const long long v = i < n ? (long long)n_in[i] : 0ll;
-    long long before, all;
-    block_exclusive(v, wave_sums, tid, before, all);
-    if (i < n) base[i] = running + before;
-    running += all;
-  }
-  if (tid == 0) *total = running;
+  const long long all = block_scan::block_offsets(n_in, n, first ? (long long)*first : 0ll, base, wave_sums, threadIdx.x);
+  if (threadIdx.x == 0) *total = all;
 }
 
 struct WriteArgs {
@@ -266,14 +231,7 @@ __global__ __launch_bounds__(kBlock) void runs_write_kernel(WriteArgs a) {
   }
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return 1;
-  }
-  return 0;
-}
+LAUNCH_CHECK_DEFINE_LAUNCHED()
 
 }  // namespace
 }  // namespace deva_runs

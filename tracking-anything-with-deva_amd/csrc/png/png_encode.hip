@@ -24,6 +24,8 @@
 // info, at places that depend on sizes and scanned counts alone.
 #include <hip/hip_runtime.h>
 
+#include "../block_scan.h"
+#include "../launch_check.h"
 #include "png_plan.h"
 
 namespace deva_png {
@@ -42,37 +44,9 @@ static_assert(9 * 1023 + 9 + 13 * ((DEVA_PNG_MAX_SIDE * 3) / 258) + 18 + 3 + 7 +
 static_assert(kStageBytes % 16 == 0 && kStageBytes >= 15 + DEVA_PNG_STEP + 3 + 15 && 2 * kPieces <= kBlock, "the staged window");
 typedef unsigned long long u64;
 
-struct Sum {
-  template <typename V>
-  __device__ __forceinline__ static V of(V a, V b) { return a + b; }
-};
-struct Max {
-  template <typename V>
-  __device__ __forceinline__ static V of(V a, V b) { return a > b ? a : b; }
-};
-
-// -> (Op over the lanes before this one in the workgroup, or `none`; Op over the workgroup); two barriers
-template <typename Op, typename V>
-__device__ __forceinline__ void block_exclusive(V v, V none, V* wave_parts, int tid, V& before, V& all) {
-  const int lane = tid & 63, wave = tid >> 6;
-  V inclusive = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const V up = __shfl_up(inclusive, d);
-    if (lane >= d) inclusive = Op::of(inclusive, up);
-  }
-  if (lane == 63) wave_parts[wave] = inclusive;
-  const V up = __shfl_up(inclusive, 1);
-  __syncthreads();
-  before = lane ? up : none;
-  all = none;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    if (w < wave) before = Op::of(before, wave_parts[w]);
-    all = Op::of(all, wave_parts[w]);
-  }
-  __syncthreads();   // wave_parts is written again in the next scan
-}
+using block_scan::block_exclusive;
+using block_scan::Max;
+using block_scan::Sum;
 
 // ------------------------------------------------------------------------------------------ Z3 / Z4
 __device__ __forceinline__ int literal_bits(int b) { return b < 144 ? 8 : 9; }
@@ -342,14 +316,7 @@ __global__ __launch_bounds__(kBlock) void place_kernel(PlaceArgs a) {
   for (int64_t i = tid; i < bytes; i += kBlock) a.out[at + i] = slot[i];
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return 1;
-  }
-  return 0;
-}
+LAUNCH_CHECK_DEFINE_LAUNCHED()
 
 void place(const struct deva_png_plan& plan, const Scratch& sc, int height, uint8_t* out, int64_t capacity, int64_t* info, hipStream_t st) {
   const PlaceArgs p = {sc.sizes,      sc.sums, sc.offsets, sc.slots, plan.slot_bytes, out, capacity, info, plan.segments, height,

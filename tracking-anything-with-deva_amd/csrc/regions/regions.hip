@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
+#include "../launch_check.h"
 #include "region_plan.h"
 #include "region_union.h"
 
@@ -285,14 +286,7 @@ void launch_labelling(const struct deva_regions_plan& plan, const Pass& ps, int 
   hipLaunchKernelGGL(regions_flatten_kernel<COUNT>, dim3(pixel_grid), dim3(kBlock), 0, st, ps);
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return 1;
-  }
-  return 0;
-}
+LAUNCH_CHECK_DEFINE_LAUNCHED()
 
 }  // namespace
 }  // namespace deva_regions

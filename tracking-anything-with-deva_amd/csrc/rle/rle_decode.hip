@@ -17,6 +17,7 @@
 // issued only for a piece whose every element is a pixel of the tile.
 #include <hip/hip_runtime.h>
 
+#include "../launch_check.h"
 #include "rle_plan.h"
 #include "rle_walk.h"
 
@@ -101,14 +102,7 @@ __global__ __launch_bounds__(kBlock) void rle_decode_kernel(Args a) {
   }
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return 1;
-  }
-  return 0;
-}
+LAUNCH_CHECK_DEFINE_LAUNCHED()
 
 }  // namespace
 }  // namespace deva_rle

@@ -16,6 +16,8 @@
 // inter (d * pitch + g, g < G), area_d and area_g.
 #include <hip/hip_runtime.h>
 
+#include "../block_scan.h"
+#include "../launch_check.h"
 #include "overlap_walk.h"
 #include "rle_overlap_plan.h"
 
@@ -35,19 +37,9 @@ struct ScanArgs {
   int d, g;
 };
 
-// inclusive scan over the wave
-__device__ __forceinline__ int wave_inclusive(int v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(v, d);
-    if (lane >= d) v += up;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(kBlock) void overlap_scan_kernel(ScanArgs a) {
   __shared__ int wave_sums[kWaves];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   for (int m = blockIdx.x; m < a.d + a.g; m += gridDim.x) {   // (uniform over the workgroup)
     const bool gt = m >= a.d;
     const int k = gt ? m - a.d : m, n = gt ? a.g : a.d;
@@ -65,16 +57,10 @@ __global__ __launch_bounds__(kBlock) void overlap_scan_kernel(ScanArgs a) {
         v[e] = ((i & 1) && i + 1 < words) ? s[i + 1] - s[i] : 0;
         sum += v[e];
       }
-      const int inclusive = wave_inclusive(sum, lane);
-      if (lane == 63) wave_sums[wave] = inclusive;
-      __syncthreads();
-      int here = running + inclusive - sum;
-#pragma unroll
-      for (int w = 0; w < kWaves; ++w) {
-        if (w < wave) here += wave_sums[w];
-        running += wave_sums[w];
-      }
-      __syncthreads();   // wave_sums is written again in the next step
+      int here, all;
+      block_scan::block_exclusive<block_scan::Sum>(sum, 0, wave_sums, tid, here, all);
+      here += running;
+      running += all;
       if (before) {
 #pragma unroll
         for (int e = 0; e < kScanItems; ++e) {
@@ -137,14 +123,7 @@ __global__ __launch_bounds__(kBlock) void overlap_pair_kernel(PairArgs a) {
   }
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return 1;
-  }
-  return 0;
-}
+LAUNCH_CHECK_DEFINE_LAUNCHED()
 
 }  // namespace
 }  // namespace deva_overlap

@@ -23,6 +23,8 @@
 // runs[0, words_cap) and info, at places that depend on indices alone.
 #include <hip/hip_runtime.h>
 
+#include "../block_scan.h"
+#include "../launch_check.h"
 #include "rle_text_plan.h"
 
 namespace deva_text {
@@ -32,32 +34,10 @@ static_assert(kBlock == 256 && kItems * kBlock == DEVA_TEXT_SCAN_CHUNK && DEVA_T
 constexpr int kWaves = kBlock / 64;
 typedef unsigned long long u64;
 
-// inclusive scan over the wave
-template <typename V>
-__device__ __forceinline__ V wave_inclusive(V v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const V up = __shfl_up(v, d);
-    if (lane >= d) v += up;
-  }
-  return v;
-}
-
 // -> (the sum of the lanes before this one in the workgroup, the workgroup's sum); two barriers
 template <typename V>
-__device__ __forceinline__ void block_exclusive(V v, V* wave_sums, int tid, V& before, V& all) {
-  const int lane = tid & 63, wave = tid >> 6;
-  const V inclusive = wave_inclusive(v, lane);
-  if (lane == 63) wave_sums[wave] = inclusive;
-  __syncthreads();
-  before = inclusive - v;
-  all = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    if (w < wave) before += wave_sums[w];
-    all += wave_sums[w];
-  }
-  __syncthreads();   // wave_sums is written again in the next step
+__device__ __forceinline__ void block_exclusive(V v, V (&wave_sums)[kWaves], int tid, V& before, V& all) {
+  block_scan::block_exclusive<block_scan::Sum>(v, (V)0, wave_sums, tid, before, all);
 }
 
 // ------------------------------------------------------------------------------------------ encode
@@ -124,17 +104,8 @@ __global__ __launch_bounds__(kBlock) void text_len_kernel(EncodeArgs a, int32_t*
 __global__ __launch_bounds__(kBlock) void text_base_kernel(const int32_t* text_len, int n, const int64_t* first, int64_t* text_base,
                                                            int64_t* text_total) {
   __shared__ long long wave_sums[kWaves];
-  const int tid = threadIdx.x;
-  long long running = first ? (long long)*first : 0ll;
-  for (int begin = 0; begin < n; begin += DEVA_TEXT_MASK_CHUNK) {
-    const int i = begin + tid;
-    const long long v = i < n ? (long long)text_len[i] : 0ll;
-    long long before, all;
-    block_exclusive(v, wave_sums, tid, before, all);
-    if (i < n) text_base[i] = running + before;
-    running += all;
-  }
-  if (tid == 0) *text_total = running;
+  const long long all = block_scan::block_offsets(text_len, n, first ? (long long)*first : 0ll, text_base, wave_sums, threadIdx.x);
+  if (threadIdx.x == 0) *text_total = all;
 }
 
 __global__ __launch_bounds__(kBlock) void text_write_kernel(EncodeArgs a, const int64_t* text_base, uint8_t* chars, int64_t capacity) {
@@ -358,14 +329,7 @@ __global__ __launch_bounds__(kBlock) void starts_kernel(ParseArgs a) {
   if (flags) atomicOr(reinterpret_cast<u64*>(a.info), (u64)flags);
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return 1;
-  }
-  return 0;
-}
+LAUNCH_CHECK_DEFINE_LAUNCHED()
 
 }  // namespace
 }  // namespace deva_text

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
+#include "../plane_values.h"
 #include "boundary_plan.h"
 
 namespace deva_vos {
@@ -29,38 +30,18 @@ namespace {
 constexpr int S = DEVA_VOS_STRIP;
 static_assert(kBlock == kWave * 4, "match_kernel keeps 4 fields of 64 objects, one per lane of the workgroup");
 
-// the raw value of pixel i of a plane as an int; an int64 outside the int range becomes -1 (non-zero, and in no table)
-template <int ENC>
-__device__ __forceinline__ int load_value(const void* plane, int64_t i) {
-  if constexpr (ENC == DEVA_VOS_U8) return (int)static_cast<const uint8_t*>(plane)[i];
-  else if constexpr (ENC == DEVA_VOS_I32) return static_cast<const int*>(plane)[i];
-  else if constexpr (ENC == DEVA_VOS_I64) {
-    const long long v = static_cast<const long long*>(plane)[i];
-    return v < (long long)INT_MIN || v > (long long)INT_MAX ? -1 : (int)v;
-  } else return (int)static_cast<const short*>(plane)[i];
-}
+using plane_values::bit_of;
+using plane_values::load_value;
+static_assert(DEVA_VOS_U8 == plane_values::kU8 && DEVA_VOS_I32 == plane_values::kI32 && DEVA_VOS_I64 == plane_values::kI64 &&
+                  DEVA_VOS_INDEX16 == plane_values::kIndex16,
+              "the encodings of plane_values.h");
 
 // R1: the slot of a value, -1 for none
 template <int ENC>
 __device__ __forceinline__ int find_slot(int value, bool binary, const int* table, int n, const uint16_t* lut, int channels) {
   if (binary) return value != 0 ? 0 : -1;
-  if constexpr (ENC == DEVA_VOS_INDEX16) {
-    if (value < 0 || value >= channels) return -1;
-    const int e = (int)lut[value];
-    return e < n ? e : -1;
-  } else {
-    if (value < 1) return -1;
-    int lo = 0, hi = n;  // the first entry >= value
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (table[mid] < value) lo = mid + 1;
-      else hi = mid;
-    }
-    return lo < n && table[lo] == value ? lo : -1;
-  }
+  return plane_values::find_slot<ENC>(value, table, n, lut, channels);
 }
-
-__device__ __forceinline__ uint64_t bit_of(int slot) { return slot >= 0 ? 1ull << slot : 0ull; }
 
 // R2 for one pixel: own slot a against the slots of the E / S / SE neighbours that exist
 __device__ __forceinline__ uint64_t boundary_word(int a, int e, int s, int se, bool has_e, bool has_s) {

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import DevaHipError, _native, ops, rle_text
+from ._pending import out_tensor, record_event, require_on_device, to_pinned
 from .ops import _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -156,11 +157,6 @@ def chunks(n: int, size: Tuple[int, int], max_masks: int, max_scratch: int, fn: 
     return [(lo, min(lo + step, n)) for lo in range(0, n, step)]
 
 
-def _on_device(t: torch.Tensor, name: str, fn: str) -> None:
-    if not t.is_cuda:
-        raise DevaHipError(f'{fn}: {name} must live on the HIP device (got {t.device}); there is no CPU path')
-
-
 # ------------------------------------------------------------------------------------------ the two calls of the library
 def _launch_count(planes, code, threshold, scratch, n_out, base, total, first, stats) -> None:
     """deva_runs_count on the current stream of the planes' device (the tests' CPU contract replaces this and `_launch_write`)"""
@@ -168,7 +164,7 @@ def _launch_count(planes, code, threshold, scratch, n_out, base, total, first, s
     for name, t in (('planes', planes), ('scratch', scratch), ('n', n_out), ('base', base), ('total', total), ('first', first),
                     ('stats', stats)):
         if t is not None:
-            _on_device(t, name, fn)
+            require_on_device(t, name, fn)
     n, h, w = planes.shape
     with torch.cuda.device(planes.device):
         check(lib().deva_runs_count(planes.data_ptr(), code, threshold, n, h, w, scratch.data_ptr(), scratch.numel() * 4, n_out.data_ptr(),
@@ -179,7 +175,7 @@ def _launch_count(planes, code, threshold, scratch, n_out, base, total, first, s
 def _launch_write(n, h, w, scratch, base, bounds, capacity) -> None:
     fn = 'write'
     for name, t in (('scratch', scratch), ('base', base), ('bounds', bounds)):
-        _on_device(t, name, fn)
+        require_on_device(t, name, fn)
     with torch.cuda.device(scratch.device):
         check(lib().deva_runs_write(n, h, w, scratch.data_ptr(), scratch.numel() * 4, base.data_ptr(),
                                     bounds.data_ptr() if capacity else None, capacity, _stream(scratch.device)), 'deva_runs_write')
@@ -194,15 +190,6 @@ class Counted(NamedTuple):
     scratch: torch.Tensor           # int32: the offsets and words `write` reads
     height: int
     width: int
-
-
-def _out(out: Optional[dict], name: str, shape, dtype, device, fn: str) -> torch.Tensor:
-    t = None if out is None else out.get(name)
-    if t is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise DevaHipError(f'{fn}: out[{name!r}] must be a contiguous {dtype} {list(shape)}')
-    return t
 
 
 def count(planes: torch.Tensor, threshold: Optional[float] = None, *, stats: bool = False, first: Optional[torch.Tensor] = None,
@@ -220,10 +207,10 @@ def count(planes: torch.Tensor, threshold: Optional[float] = None, *, stats: boo
     nbytes = runs_scratch(n, (h, w))
     if nbytes < 0:
         raise DevaHipError(f'{fn}: {n} masks of {h} x {w} are above the limits of one call: {lib().deva_runs_last_error().decode()}')
-    counted = Counted(_out(out, 'n', (n,), torch.int32, device, fn), _out(out, 'base', (n,), torch.int64, device, fn),
-                      _out(out, 'total', (1,), torch.int64, device, fn),
-                      _out(out, 'stats', (n, 5), torch.int32, device, fn) if stats else None,
-                      _out(out, 'scratch', (nbytes // 4,), torch.int32, device, fn), h, w)
+    counted = Counted(out_tensor(out, 'n', (n,), torch.int32, device, fn), out_tensor(out, 'base', (n,), torch.int64, device, fn),
+                      out_tensor(out, 'total', (1,), torch.int64, device, fn),
+                      out_tensor(out, 'stats', (n, 5), torch.int32, device, fn) if stats else None,
+                      out_tensor(out, 'scratch', (nbytes // 4,), torch.int32, device, fn), h, w)
     if n:
         _launch_count(planes, code, threshold, counted.scratch, counted.n, counted.base, counted.total, first, counted.stats)
     elif first is not None:
@@ -249,14 +236,6 @@ def write(counted: Counted, bounds: torch.Tensor, capacity: Optional[int] = None
 
 
 # ------------------------------------------------------------------------------------------ encode
-def _to_pinned(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        return t
-    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-    host.copy_(t, non_blocking=True)
-    return host
-
-
 class PendingRuns:
     """an encoding whose results are on their way to the host; `finish()` waits for them"""
 
@@ -371,13 +350,9 @@ def encode(planes: torch.Tensor, *, threshold: Optional[float] = None, form: str
     bounds = torch.empty(room, dtype=torch.int32, device=device)
     for part in counted:
         write(part, bounds, room)
-    event = None
     coded = rle_text.encode_text(n_dev, base, bounds, (h, w), pending=True, record=False) if on_device else None
-    host = [_to_pinned(t) if t is not None else None for t in (n_dev, None if on_device else bounds, totals, stats_dev)]
-    if device.type == 'cuda':
-        event = torch.cuda.Event()
-        event.record(torch.cuda.current_stream(device))
-    pending = PendingRuns((h, w), form, host[0], host[1], host[2], host[3], room, event, coded)
+    host = [to_pinned(t) if t is not None else None for t in (n_dev, None if on_device else bounds, totals, stats_dev)]
+    pending = PendingRuns((h, w), form, host[0], host[1], host[2], host[3], room, record_event(device), coded)
     return pending.finish() if capacity is None else pending
 
 

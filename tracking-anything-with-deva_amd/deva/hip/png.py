@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import DevaHipError, _native
+from ._pending import record_event, require_on_device, to_pinned
 from .ops import _stream
 
 __all__ = ['encode', 'deflate', 'plan', 'limits', 'file_bytes', 'PendingPng', 'PlanInfo', 'LimitInfo', 'MAX_SIDE', 'MAX_BYTES',
@@ -123,16 +124,11 @@ def plan(height: int, width: int, bpp: int = 1) -> PlanInfo:
 
 
 # ------------------------------------------------------------------------------------------ the two calls of the library
-def _on_device(t: torch.Tensor, name: str, fn: str) -> None:
-    if not t.is_cuda:
-        raise DevaHipError(f'{fn}: {name} must live on the HIP device (got {t.device}); there is no CPU path')
-
-
 def _launch_deflate(plane, h, w, bpp, scratch, out, capacity, info) -> None:
     """deva_png_deflate on the current stream of the plane's device (the tests' CPU contract replaces the two `_launch_*`)"""
     fn = 'deflate'
     for name, t in (('plane', plane), ('scratch', scratch), ('out', out), ('info', info)):
-        _on_device(t, name, fn)
+        require_on_device(t, name, fn)
     with torch.cuda.device(plane.device):
         check(lib().deva_png_deflate(plane.data_ptr(), h, w, bpp, scratch.data_ptr(), scratch.numel(), out.data_ptr() if capacity else None,
                                      capacity, info.data_ptr(), _stream(plane.device)), 'deva_png_deflate')
@@ -141,7 +137,7 @@ def _launch_deflate(plane, h, w, bpp, scratch, out, capacity, info) -> None:
 def _launch_place(h, w, bpp, scratch, out, capacity, info) -> None:
     fn = 'deflate'
     for name, t in (('scratch', scratch), ('out', out), ('info', info)):
-        _on_device(t, name, fn)
+        require_on_device(t, name, fn)
     with torch.cuda.device(scratch.device):
         check(lib().deva_png_place(h, w, bpp, scratch.data_ptr(), scratch.numel(), out.data_ptr() if capacity else None, capacity,
                                    info.data_ptr(), _stream(scratch.device)), 'deva_png_place')
@@ -188,14 +184,6 @@ def _palette(fn: str, palette, bpp: int) -> Optional[bytes]:
     if len(data) == 0 or len(data) > 768 or len(data) % 3:
         raise DevaHipError(f'{fn}: palette: 1 to 256 RGB triples, 768 bytes at most (got {len(data)} bytes)')
     return data
-
-
-def _to_pinned(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        return t.clone()
-    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-    host.copy_(t, non_blocking=True)
-    return host
 
 
 class PendingPng:
@@ -250,11 +238,8 @@ def _run(fn: str, plane, palette, capacity, stream, as_file: bool):
             total = int(info.cpu()[0])
             data = out[:total].cpu().numpy().tobytes()
             return file_bytes(data, h, w, bpp, palette) if as_file else data
-        host_out, host_info = _to_pinned(out[:room]), _to_pinned(info)
-        event = None
-        if device.type == 'cuda':
-            event = torch.cuda.Event()
-            event.record(torch.cuda.current_stream(device))
+        host_out, host_info = to_pinned(out[:room]), to_pinned(info)
+        event = record_event(device)
     return PendingPng((h, w, bpp), palette, as_file, scratch, out, info, room, host_out, host_info, event)
 
 

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import DevaHipError, _native
+from ._pending import out_tensor, record_event, require_on_device, to_pinned
 from .ops import _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -172,7 +173,7 @@ def _parse_sides(dt: Sequence, gt: Sequence, source_size, fn: str, parse: str = 
     for b in waiting:
         b.pending.fetch()
     if waiting:
-        event = rle.rle_text._event(waiting[0].pending.device)
+        event = record_event(waiting[0].pending.device)
         if event is not None:
             event.synchronize()
     for k, b in enumerate(begun):
@@ -244,22 +245,12 @@ def _launch(dt: _Side, gt: _Side, height: int, width: int, scratch, inter, area_
     row-major table, its row pitch the table's"""
     fn = 'intersections'
     for name, t in (('dt', dt.device), ('gt', gt.device), ('scratch', scratch), ('inter', inter), ('area_d', area_d), ('area_g', area_g)):
-        if not t.is_cuda:
-            raise DevaHipError(f'{fn}: {name} must live on the HIP device (got {t.device}); there is no CPU path')
+        require_on_device(t, name, fn)
     check(lib().deva_overlap_intersections(
         dt.host.data_ptr(), dt.device.data_ptr(), dt.words, dt.n, gt.host.data_ptr(), gt.device.data_ptr(), gt.words, gt.n, height, width,
         dt.device.data_ptr() + 4 * dt.words, gt.device.data_ptr() + 4 * gt.words, scratch.data_ptr(), scratch.numel() * 4,
         inter.data_ptr(), max(inter.stride(0), inter.shape[1]), area_d.data_ptr(),
         area_g.data_ptr(), stream), 'deva_overlap_intersections')
-
-
-def _out(out: Optional[dict], name: str, shape, device, fn: str) -> torch.Tensor:
-    t = None if out is None else out.get(name)
-    if t is None:
-        return torch.empty(shape, dtype=torch.int32, device=device)
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise DevaHipError(f'{fn}: out[{name!r}] must be a contiguous torch.int32 {list(shape)}')
-    return t
 
 
 class PendingOverlap:
@@ -276,14 +267,6 @@ class PendingOverlap:
             self._result = tuple(t.numpy().astype(np.int64) for t in self._host)
             self._host = None
         return self._result
-
-
-def _to_pinned(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        return t
-    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-    host.copy_(t, non_blocking=True)
-    return host
 
 
 def intersections(dt: Sequence, gt: Sequence, *, stream=None, source_size: Optional[Tuple[int, int]] = None, device=None,
@@ -331,8 +314,8 @@ def intersections(dt: Sequence, gt: Sequence, *, stream=None, source_size: Optio
     blocks = [(pd, pg) for pd in _parts(parsed_d, *top, f'{fn}: dt') for pg in _parts(parsed_g, *top, f'{fn}: gt')]
     given = [t for t in (out or {}).values() if isinstance(t, torch.Tensor)]
     device = torch.device(device if device is not None else (given[0].device if given else (stream.device if stream is not None else 'cuda')))
-    inter = _out(out, 'inter', (n_d, n_g), device, fn)
-    area_d, area_g = _out(out, 'area_d', (n_d,), device, fn), _out(out, 'area_g', (n_g,), device, fn)
+    inter = out_tensor(out, 'inter', (n_d, n_g), torch.int32, device, fn)
+    area_d, area_g = out_tensor(out, 'area_d', (n_d,), torch.int32, device, fn), out_tensor(out, 'area_g', (n_g,), torch.int32, device, fn)
     on_gpu = device.type == 'cuda'
     sides = {}
     for (lo_d, hi_d), (lo_g, hi_g) in blocks:             # every chunk built and checked before the first launch of the call
@@ -362,12 +345,8 @@ def intersections(dt: Sequence, gt: Sequence, *, stream=None, source_size: Optio
             _launch(side_d, side_g, h, w, scratch, inter[lo_d:hi_d, lo_g:hi_g], area_d[lo_d:hi_d], area_g[lo_g:hi_g], handle)
         if not pending:
             return inter, area_d, area_g
-        host = [_to_pinned(t) for t in (inter, area_d, area_g)]
-        event = None
-        if on_gpu:
-            event = torch.cuda.Event()
-            event.record(torch.cuda.current_stream(device))
-        return PendingOverlap(host[0], host[1], host[2], event)
+        host = [to_pinned(t) for t in (inter, area_d, area_g)]
+        return PendingOverlap(host[0], host[1], host[2], record_event(device))
 
 
 def iou_from_counts(inter: np.ndarray, area_d: np.ndarray, area_g: np.ndarray, iscrowd=None) -> np.ndarray:

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import DevaHipError, _native
+from ._pending import record_event, require_on_device, to_pinned
 from .ops import _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -121,18 +122,13 @@ def parse_scratch(n: int) -> int:
 
 
 # ------------------------------------------------------------------------------------------ the three calls of the library
-def _on_device(t: torch.Tensor, name: str, fn: str) -> None:
-    if not t.is_cuda:
-        raise DevaHipError(f'{fn}: {name} must live on the HIP device (got {t.device}); there is no CPU path')
-
-
 def _launch_encode_count(n, base, bounds, bounds_len, h, w, text_len, text_base, text_total, first) -> None:
     """deva_text_encode_count on the current stream of the inputs' device (the tests' CPU contract replaces the three `_launch_*`)"""
     fn = 'encode_count'
     for name, t in (('n', n), ('base', base), ('bounds', bounds), ('text_len', text_len), ('text_base', text_base), ('text_total', text_total),
                     ('first', first)):
         if t is not None:
-            _on_device(t, name, fn)
+            require_on_device(t, name, fn)
     with torch.cuda.device(n.device):
         check(lib().deva_text_encode_count(n.data_ptr(), base.data_ptr(), bounds.data_ptr() if bounds_len else None, bounds_len, n.numel(), h, w,
                                            text_len.data_ptr(), text_base.data_ptr(), text_total.data_ptr(),
@@ -142,7 +138,7 @@ def _launch_encode_count(n, base, bounds, bounds_len, h, w, text_len, text_base,
 def _launch_encode_write(n, base, bounds, bounds_len, h, w, text_base, chars, capacity) -> None:
     fn = 'encode_write'
     for name, t in (('n', n), ('base', base), ('bounds', bounds), ('text_base', text_base), ('chars', chars)):
-        _on_device(t, name, fn)
+        require_on_device(t, name, fn)
     with torch.cuda.device(n.device):
         check(lib().deva_text_encode_write(n.data_ptr(), base.data_ptr(), bounds.data_ptr() if bounds_len else None, bounds_len, n.numel(), h, w,
                                            text_base.data_ptr(), chars.data_ptr() if capacity else None, capacity, _stream(n.device)),
@@ -152,7 +148,7 @@ def _launch_encode_write(n, base, bounds, bounds_len, h, w, text_base, chars, ca
 def _launch_parse(chars, chars_len, text_first, n, h, w, scratch, runs, words_cap, info) -> None:
     fn = 'parse'
     for name, t in (('chars', chars), ('text_first', text_first), ('scratch', scratch), ('runs', runs), ('info', info)):
-        _on_device(t, name, fn)
+        require_on_device(t, name, fn)
     with torch.cuda.device(runs.device):
         check(lib().deva_text_parse(chars.data_ptr() if chars_len else None, chars_len, text_first.data_ptr(), n, h, w,
                                     scratch.data_ptr() if n else None, scratch.numel() * 4, runs.data_ptr(), words_cap, info.data_ptr(),
@@ -164,22 +160,6 @@ def _size(size, fn: str) -> Tuple[int, int]:
     if h < 1 or w < 1 or h * w >= 2**31:
         raise DevaHipError(f'{fn}: bad height x width {h} x {w} (1 <= H * W < 2^31)')
     return h, w
-
-
-def _to_pinned(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        return t.clone()
-    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-    host.copy_(t, non_blocking=True)
-    return host
-
-
-def _event(device) -> Optional['torch.cuda.Event']:
-    if torch.device(device).type != 'cuda':
-        return None
-    event = torch.cuda.Event()
-    event.record(torch.cuda.current_stream(device))
-    return event
 
 
 # ------------------------------------------------------------------------------------------ encode
@@ -253,8 +233,8 @@ def encode_text(n: torch.Tensor, base: torch.Tensor, bounds: torch.Tensor, size:
                              totals[c:c + 1])
     for lo, hi in parts:
         _launch_encode_write(n[lo:hi], base[lo:hi], bounds, bounds.numel(), h, w, text_base[lo:hi], chars, room)
-    host = [_to_pinned(t) for t in (chars, text_len, totals)]
-    result = PendingText(host[0], host[1], host[2], room, _event(device) if record else None)
+    host = [to_pinned(t) for t in (chars, text_len, totals)]
+    result = PendingText(host[0], host[1], host[2], room, record_event(device) if record else None)
     return result if pending else result.finish()
 
 
@@ -308,8 +288,8 @@ class PendingParse:
             scratch = torch.empty(max(2 * n, 1), dtype=torch.int32, device=self.device)
             info = torch.empty(2, dtype=torch.int64, device=self.device)
             _launch_parse(up_d[8 * (n + 1):], total, up_d[:8 * (n + 1)].view(torch.int64), n, h, w, scratch, runs, words_cap, info)
-            self._chunks.append((lo, hi, runs, _to_pinned(info), up))
-        self._event = _event(self.device)
+            self._chunks.append((lo, hi, runs, to_pinned(info), up))
+        self._event = record_event(self.device)
         self._result = None
 
     def flags(self) -> int:
@@ -324,7 +304,7 @@ class PendingParse:
 
     def fetch(self) -> None:
         """after `flags()` gave 0: start the copies of the words that `info` counts (the caller waits for them: `complete`)"""
-        self._hosts = [_to_pinned(runs[:int(info[1])]) for _, _, runs, info, _ in self._chunks]
+        self._hosts = [to_pinned(runs[:int(info[1])]) for _, _, runs, info, _ in self._chunks]
 
     def complete(self) -> List[RunChunk]:
         """after `fetch()` and a wait for its copies"""
@@ -344,7 +324,7 @@ class PendingParse:
                     on_flags(flags)
                 raise DevaHipError('parse_text: ' + '; '.join(text for bit, text in FLAGS.items() if flags & bit))
             self.fetch()
-            event = _event(self.device)
+            event = record_event(self.device)
             if event is not None:
                 event.synchronize()
             self.complete()
