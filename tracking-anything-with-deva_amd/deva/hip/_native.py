@@ -1,5 +1,5 @@
-"""What the eleven bindings (`deva.hip`, `deva.hip.metrics`, `deva.hip.vos_metrics`, `deva.hip.pair_metrics`, `deva.hip.regions`,
-`deva.hip.rle`, `deva.hip.mask_runs`, `deva.hip.rle_overlap`, `deva.hip.rle_text`, `deva.hip.lowres`, `deva.hip.png`) do alike: load a library and check it against the module's `SIGNATURES` and `ABI_VERSION`, and turn a non-zero return code
+"""What the twelve bindings (`deva.hip`, `deva.hip.metrics`, `deva.hip.vos_metrics`, `deva.hip.pair_metrics`, `deva.hip.regions`,
+`deva.hip.rle`, `deva.hip.mask_runs`, `deva.hip.rle_overlap`, `deva.hip.rle_text`, `deva.hip.lowres`, `deva.hip.png`, `deva.hip.jpeg`) do alike: load a library and check it against the module's `SIGNATURES` and `ABI_VERSION`, and turn a non-zero return code
 into a `DevaHipError`.  Each module keeps its own `LIB_PATH` (read when `lib()` first loads, so a tool may point it elsewhere
 before that), `_LIB` and texts."""
 import ctypes

@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from deva.hip import ops, png as png_coder, rle
+from deva.hip import jpeg as jpeg_coder, ops, png as png_coder, rle
 
 # ------------------------------------------------------------------------------------------ colours
 def long_id_colors(ids: Sequence[int]) -> np.ndarray:
@@ -124,6 +124,7 @@ class PendingFrame:
         self.host_stats, self.n, self.host_bounds, self.host_planes, self.event = host_stats, n, host_bounds, host_planes, event
         self.channel_ids = None
         self.png = None          # a `deva.hip.png.PendingPng` when the saver codes the PNG on the device
+        self.jpeg = None         # a `deva.hip.jpeg.PendingJpeg` when the saver codes the overlay JPEG on the device
 
     def finish(self) -> FrameResult:
         if self.event is not None:
@@ -244,12 +245,20 @@ class FrameResultSaver:
     that adapts -- 64 KB at first, then twice the largest stream seen; a longer stream is copied a second time at its
     exact size -- and the worker wraps the copied stream into the file (chunks and CRCs on the host) and writes the bytes
     to the same path.  The file decodes to the same pixels and palette; its bytes are not PIL's and it is two to four
-    times as large.  The `blend` JPEG stays with PIL, and `FrameResult.host` then lacks the PNG's plane."""
+    times as large.  `FrameResult.host` then lacks the PNG's plane.
+
+    `jpeg='host'` (the default): PIL codes the `blend` overlay of the `demo` dataset on the worker.  With `jpeg='device'`
+    `blend` is not copied to the host either: `deva.hip.jpeg.encode` codes the entropy-coded data of a baseline JPEG
+    (quality 75, 4:2:0, a restart interval per MCU row: include/deva_jpeg.h) on the caller's stream, with a capacity that
+    adapts like the PNG's -- 256 KB at first -- and the worker puts the markers around the copied data and writes the bytes
+    to the same `Visualizations/.../NAME.jpg`.  The file is not PIL's bytes: it decodes to within a few hundredths of a
+    dB of PIL's file at a size within a few percent.  The two options are independent of each other."""
 
     PNG_FIRST_CAPACITY = 65536
+    JPEG_FIRST_CAPACITY = 262144
 
     def __init__(self, output_root: str, video_name: str, *, dataset: str, object_manager, palette=None,
-                 id_postprocessor=None, frame_hook=None, png: str = 'host'):
+                 id_postprocessor=None, frame_hook=None, png: str = 'host', jpeg: str = 'host'):
         self.output_root = output_root
         self.video_name = video_name
         self.dataset = dataset.lower()
@@ -264,6 +273,11 @@ class FrameResultSaver:
         self.png = png
         self.png_capacity = self.PNG_FIRST_CAPACITY
         self.png_largest = 0
+        if jpeg not in ('host', 'device'):
+            raise ValueError(f"jpeg: 'host' or 'device' (got {jpeg!r})")
+        self.jpeg = jpeg
+        self.jpeg_capacity = self.JPEG_FIRST_CAPACITY
+        self.jpeg_largest = 0
         self.need_remapping = False
         self.json_style = None
         self.output_postfix = None
@@ -321,11 +335,15 @@ class FrameResultSaver:
         pending = launch_frame(self.object_manager, prob, shape if need_resize else None,
                                image=image_np if 'blend' in planes else None, rle=self.json_style == 'burst',
                                color='id' if long_id else 'gray', remap=self.need_remapping, planes=planes,
-                               host=planes if self.png == 'host' else planes[1:],
+                               host=planes if self.png == self.jpeg == 'host' else [
+                                   p for k, p in enumerate(planes)
+                                   if not (self.png == 'device' and k == 0) and not (self.jpeg == 'device' and p == 'blend')],
                                id_map=None if merge is None else merge[0], index=self.frame_hook is not None)
         if self.png == 'device' and save_the_mask:   # the stream is coded now, on the caller's stream; nothing is waited for
             plane = pending.products.color if long_id else pending.products.gray
             pending.png = png_coder.encode(plane, palette=None if long_id else self.palette, capacity=self.png_capacity)
+        if self.jpeg == 'device' and 'blend' in planes:   # likewise the overlay's JPEG
+            pending.jpeg = jpeg_coder.encode(pending.products.blend, capacity=self.jpeg_capacity)
         self.queue.put((pending, frame_name, long_id) if merge is None else (pending, frame_name, long_id, merge))
 
     def end(self) -> None:
@@ -394,6 +412,11 @@ class FrameResultSaver:
             if 'blend' in result.host:
                 self._save_image(Image.fromarray(result.host['blend']),
                                  path.join(self._out_dir(self.visualize_postfix), frame_name[:-4] + '.jpg'))
+        if pending.jpeg is not None:
+            data = pending.jpeg.finish()
+            self.jpeg_largest = max(self.jpeg_largest, pending.jpeg.total)
+            self.jpeg_capacity = 2 * self.jpeg_largest
+            self._save_bytes(data, path.join(self._out_dir(self.visualize_postfix), frame_name[:-4] + '.jpg'))
         if self.frame_hook is not None:
             self.frame_hook(frame_name, result, self.all_annotations[-1] if self.json_style is not None else None)
 
